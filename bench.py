@@ -6,7 +6,14 @@ MSE loss, backward and Adam — the loop body of ``Trainer._epoch``
 (reference ``deeprank2/trainer.py:682-690``) — with the whole synthetic dataset
 already resident in HBM (a mini-batch is a list of graph ids).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(``value``, ``ms_per_step``, ...).  ``--dump-outputs DIR`` then writes what the
+last timed step computed as ``DIR/<name>.npy``.  ``--full`` adds what takes
+runs of its own: the graph pass and the reduce timed alone (``roofline``,
+``step_split_us``), the device copy bandwidth and the CPU oracle
+(``cpu_baseline``).
 
 N>1: one rank per GPU over RCCL, one global batch of 64*N graphs per step
 (weak scaling), the same global batch sequence on every rank (same seed), each
@@ -419,6 +426,40 @@ def cpu_baseline(graphs, budget_s=15.0, max_steps=60, model_name="ginet"):
     return {"value": round(len(graphs) / dt, 2), "unit": "graphs/s", "cores": cores, "host_affinity_cores": affinity, "kind": "port", "sample": f"fastest of {n} {name}(30,1,3) train steps (fwd+MSE+bwd+Adam) after {warm} warm-up step(s), on one batch of {len(graphs)} of the same synthetic graphs; oracle/gnn_ref.py on torch CPU, {cores} threads pinned to the {len(pinned) or cores} idlest CPUs (host affinity {affinity}); {dt * 1e3:.1f} ms/step (median {float(np.median(times)) * 1e3:.1f}, max {max(times) * 1e3:.1f})"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+PRIME_REPLAYS = 8  # untimed replays of the timed region's graphs before it (main)
+
+
+def dump_outputs(out_dir, step, n_graphs):
+    """``--dump-outputs``: what the last timed step left with its caller, as
+    ``<out_dir>/<name>.npy`` (float32): the ``(loss, out)`` that
+    ``FusedTrainStep.step`` returns, the gradients it reduced, and the
+    parameters and Adam moments after its update (each group flattened in
+    ``model.ordered_params()`` order).  An array past its share of
+    ``DUMP_LIMIT_BYTES`` is written as a fixed, seeded sample of its elements."""
+    import numpy as np  # noqa: PLC0415
+    import torch  # noqa: PLC0415
+
+    def flat(ts):
+        return torch.cat([t.detach().reshape(-1).float() for t in ts])
+
+    arrays = {
+        "loss": step.loss_out,
+        "out": step.out[:n_graphs],
+        "grads": step.flat_grad,
+        "params": flat(step.params),
+        "adam_m": flat([m for m, _ in step.states]),
+        "adam_v": flat([v for _, v in step.states]),
+    }
+    share = DUMP_LIMIT_BYTES // len(arrays) // 4  # float32 elements per array
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def parse_args(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -434,8 +475,10 @@ def parse_args(argv):
     ap.add_argument("--vanilla-pipeline", action="store_true", help="VanillaNetwork: the batch-wide kernel pipeline even when the per-graph kernel fits (diagnostic)")
     ap.add_argument("--acc", choices=["auto", "on", "off"], default="auto", help="GINet fp32: accumulating pass (dr_ginet_acc_pass: each workgroup sums every R-th graph's gradients on chip, one partial row per workgroup); auto = batches past the CU count")
     ap.add_argument("--no-acc-prefetch", action="store_true", help="accumulating pass without the prefetch layout (A/B: each graph stages its own inputs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stream-copy", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also time the graph pass and the reduce alone (roofline, step_split_us), the device copy bandwidth and the CPU oracle (cpu_baseline): runs of their own after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (loss, predictions, gradients, updated parameters and Adam moments) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle")
+    ap.add_argument("--no-stream-copy", action="store_true", help="--full: skip the device copy bandwidth")
     ap.add_argument("--eager", action="store_true", help="launch every step from Python instead of replaying captured HIP graphs")
     ap.add_argument("--eager-ddp", action="store_true", help="N>1: launch steps from Python (default: the RCCL all-reduce is captured in the HIP graph with the kernels)")
     ap.add_argument("--trainer", action="store_true", help="diagnostic: the drop-in path, Trainer(GINet, GraphDataset(HDF5)).train(), and the GraphDataset -> GraphStore load rate (one JSON line; not the headline)")
@@ -443,7 +486,10 @@ def parse_args(argv):
     ap.add_argument("--validate", action="store_true", help="--trainer: train(validate=True), timing each validation pass")
     ap.add_argument("--shard-policy", choices=["auto", "contiguous", "edges"], default="auto", help="N>1: how each global batch is split over the ranks (distributed.plan_shards)")
     ap.add_argument("--dry-run", action="store_true", help="launcher check without a GPU: each rank joins a gloo group, builds the global batches and its shards, rank 0 prints the JSON skeleton with the per-rank edge loads")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def global_batches(args, world, rank):
@@ -721,44 +767,56 @@ def main(args):  # noqa: PLR0915, PLR0912, C901
     layer_path = any(layered.needs_layers(step.spec, h, step.out_dim) for h in handles)
     if layer_path:
         capture_note = " (layer-level path for graphs beyond one workgroup's LDS: autograd, not capturable)"
+    # the timed steps as captured graphs: whole sweeps over the resident
+    # mini-batches (one launch per len(handles) steps), then the steps after
+    # them as one more captured graph (one launch), not one replay per step;
+    # up to 64 timed steps: all of them in one graph
+    n_sweeps, n_rest = divmod(args.steps, len(handles))
+    if args.steps <= 64:
+        n_sweeps, n_rest = 0, args.steps
+    one_rest_graph = os.environ.get("DR_BENCH_REST", "1") == "1"  # 0: the steps after the sweeps as per-step graphs (diagnostic)
+    replay = False
+    rest = None
     if not args.eager and not layer_path and (pg is None or (not shared and not args.eager_ddp)):
-        # one captured graph per resident mini-batch, plus one graph holding a
-        # whole sweep over them (one launch per len(handles) steps); N>1: the
+        # only the graphs the timed region launches are captured; N>1: the
         # RCCL all-reduce is captured with the kernels
         try:
-            captured = [step.capture(h, global_batch=B * world) for h in handles]
-            sweep = step.capture_sweep(sweep_handles, global_batch=B * world)
+            if n_sweeps:
+                sweep = step.capture_sweep(sweep_handles, global_batch=B * world)
+            if n_rest and one_rest_graph:
+                rest = step.capture_sweep([sweep_handles[i % len(handles)] for i in range(n_rest)], global_batch=B * world)
+            elif n_rest:
+                captured = [step.capture(h, global_batch=B * world) for h in handles]
+            replay = True
         except RuntimeError as e:
             if pg is None:
                 raise
-            captured = sweep = None  # fall back to eager steps
+            captured = sweep = rest = None  # fall back to eager steps
             capture_note = f" (capture failed: {str(e)[:120]})"
             print(f"[bench] rank {rank}: HIP graph capture of the DDP step failed, running eager steps: {e}", file=sys.stderr)
         if pg is not None:  # every rank runs the same launch mode
-            ok = torch.tensor([0.0 if captured is None else 1.0], device=dev)
+            ok = torch.tensor([1.0 if replay else 0.0], device=dev)
             torch.distributed.all_reduce(ok, op=torch.distributed.ReduceOp.MIN)
             if float(ok.item()) < 1.0:
-                captured = sweep = None
+                captured = sweep = rest = None
+                replay = False
                 capture_note = capture_note or " (capture failed on another rank)"
+    if not replay:
+        n_sweeps = n_rest = 0
 
-    n_sweeps = args.steps // len(handles) if sweep is not None else 0
-    # the steps after the whole sweeps: one more captured graph (one launch),
-    # not one replay per step; up to 64 timed steps: all of them in one graph
-    n_rest = args.steps - n_sweeps * len(handles) if sweep is not None else 0
-    if sweep is not None and args.steps <= 64:
-        n_sweeps, n_rest = 0, args.steps
-    rest = None
-    if n_rest and os.environ.get("DR_BENCH_REST", "1") == "1":
-        rest = step.capture_sweep([sweep_handles[i % len(handles)] for i in range(n_rest)], global_batch=B * world)
-
-    if sweep is not None:
-        # prime: replay each graph the timed region launches once (their first
+    if replay:
+        # prime: replay each graph the timed region launches (their first
         # launch uploads them), then restore the training state, so the timed
-        # region starts from the state W warmup steps left
+        # region starts from the state W warmup steps left.  PRIME_REPLAYS
+        # times: a 20-step timed region lasts 0.4 ms, and after a single
+        # replay the device was not yet at its working clocks (measured,
+        # interleaved runs of --steps 20: 19.4 us/step after one replay,
+        # 19.1 after eight)
         snap = [t.detach().clone() for t in step._state_tensors()]  # noqa: SLF001
-        for gr in [sweep if n_sweeps else None, rest, *(captured if n_rest and rest is None else [])]:
-            if gr is not None:
-                gr.replay()
+        for _ in range(PRIME_REPLAYS):
+            for gr in [sweep if n_sweeps else None, rest, *(captured if n_rest and rest is None else [])]:
+                if gr is not None:
+                    gr.replay()
         torch.cuda.synchronize()
         for t, v in zip(step._state_tensors(), snap):  # noqa: SLF001
             t.data.copy_(v)
@@ -800,28 +858,13 @@ def main(args):  # noqa: PLR0915, PLR0912, C901
         torch.distributed.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-
-    # Dominant-kernel duration: the graph pass alone, args.steps launches over
-    # the resident mini-batches captured back to back in one HIP graph and
-    # timed with HIP events on the launch stream (no host launch overhead;
-    # agrees with the rocprofv3 kernel average, profiles/).
-    # (at least 200 launches: a graph of K launches also carries the graph's
-    # own launch latency, ~9 us, which at the driver's K = 20 would add ~0.45
-    # us to every launch's average; the rocprofv3 average is the cross-check)
-    n_kernel = max(args.steps, 200)
-    kernel_ms = None if layer_path else step.time_graph_pass(handles, n_kernel, global_batch=B * world)
-    if kernel_ms is None:  # layer path: no single graph-pass kernel; price the whole step
-        kernel_ms = elapsed / args.steps * 1e3
-    # the step split (pass / reduce + Adam / the rest: launch gaps inside the
-    # replayed graphs), world of one only
-    reduce_ms = None if (layer_path or pg is not None) else step.time_reduce(handles, n_kernel, global_batch=B * world)
+    final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, handles[(args.warmup + args.steps - 1) % len(handles)].B)
     if pg is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
-        km = torch.tensor([kernel_ms], dtype=torch.float64, device=dev)
-        torch.distributed.all_reduce(km, op=torch.distributed.ReduceOp.MAX)
-        kernel_ms = float(km.item())
 
     graphs_total = B * world * args.steps
     edges_local = sum(store.edges_in(handles[(args.warmup + i) % len(handles)].gids_host) for i in range(args.steps))
@@ -829,44 +872,11 @@ def main(args):  # noqa: PLR0915, PLR0912, C901
     if pg is not None:
         torch.distributed.all_reduce(et)
     edges_total = float(et.item())
-    s = 2 if args.dtype == "bf16" else 4
-    alg = float(np.mean([algorithmic_bytes(packed, h.gids_host, args.model, s) for h in handles]))
-    design = float(np.mean([design_bytes(packed, h.gids_host, args.model) for h in handles]))
-    n_params = sum(p.numel() for p in model.parameters())
-    adam_bytes = 28 * n_params  # Adam fp32: read param, grad, m, v; write param, m, v (§8(d))
-    kernel_alg = alg
-    achieved = kernel_alg / (kernel_ms * 1e-3) / 1e9
     ms_step = elapsed / args.steps * 1e3
-    wall_gbs = (alg + adam_bytes) / (ms_step * 1e-3) / 1e9
     default_cfg = args.model == "ginet" and args.graphs == "residue" and B == B_PER_GPU and args.dtype == "f32"
-    pmc_cfg = default_cfg or (args.model in ("foutnet", "sgat", "vanilla", "ginet_nocluster") and args.graphs == "residue" and B == B_PER_GPU and args.dtype == "f32")
-    traffic, traffic_src = pmc_traffic_bytes(args.model) if pmc_cfg else (None, None)
-    large = args.model == "ginet" and (bool(args.force_large) or args.ginet_path != "auto" or args.dtype == "bf16" or any(h.lds((step.spec.entry, 1), lambda *sz: 0) > 160 * 1024 for h in handles))
-    # multi-kernel graph passes (Vanilla pipeline, GINet tile + tail kernels):
-    # the per-kernel PMC table of the same workload (tools/pmc_run.py <model>_<graphs>[_bf16])
-    if traffic is None and B == B_PER_GPU_FOR.get(args.graphs) and not args.force_large and args.ginet_path == "auto" and (
-        (args.model == "vanilla" and args.graphs in ("atom", "mixed")) or (args.model == "ginet" and args.graphs in ("atom", "mixed"))
-    ):
-        traffic, traffic_src = pmc_traffic_step(args.model, args.graphs, args.dtype)
-    copy_gbs = None if args.no_stream_copy else stream_copy_gbs(dev)
-    # §8(d) FLOP side: algorithmic FLOPs per launch against the dense MFMA peak
-    # of the compute dtype, and MFMA utilisation from the committed PMC pass
-    flops = float(np.mean([algorithmic_flops(packed, h.gids_host, args.model) for h in handles]))
-    tflops = flops / (kernel_ms * 1e-3) / 1e12
-    n_wg = B
-    if args.model == "vanilla" and not layer_path:
-        from deeprank2_amd.neuralnets.gnn.vanilla_gnn import split_k  # noqa: PLC0415
-
-        n_wg = B * split_k(handles[0], 30, 3)
-    mfma = pmc_mfma(args.model, kernel_ms, n_wg) if pmc_cfg else None
-
+    workload = WORKLOADS.get((args.model, args.graphs), f"{args.model} on {args.graphs} graphs (diagnostic)")
     result = None
     if rank == 0:
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(graphs[:B], model_name=args.model)
-        workload = WORKLOADS.get((args.model, args.graphs), f"{args.model} on {args.graphs} graphs (diagnostic)")
-        kname = "layer-level path (FoutLayer/SGAT/GINetConvLayer + pooling kernels, torch autograd): whole-step wall clock" if layer_path else {"ginet": "ginet_large_conv1_kernel + ginet_large_tail_kernel (dr_ginet_large_pass)" if large else ((f"ginet_acc_kernel (dr_ginet_acc_pass: {step._acc_rows(handles[0])} workgroups, each runs every R-th graph's fwd+loss+bwd and sums its gradients on chip; one partial row per workgroup)" if step._acc_rows(handles[0]) else "ginet_graph_kernel (dr_ginet_graph_pass, fwd+loss+bwd, 1 workgroup/graph)")), "foutnet": "fout_graph_kernel<false> (dr_fout_graph_pass)", "vanilla": "vanilla_graph_kernel (dr_vanilla_fused_pass) / vanilla pipeline (dr_vanilla_graph_pass)", "sgat": "fout_graph_kernel<true> (dr_sgat_graph_pass)", "ginet_nocluster": "ginet_nocluster_kernel (dr_ginet_nocluster_graph_pass)"}[args.model]
         result = {
             "metric": HEADLINE_METRIC if default_cfg else f"graphs/sec per training step, {workload} (fwd+MSE+bwd+Adam)",
             "value": round(graphs_total / elapsed, 1),
@@ -898,6 +908,74 @@ def main(args):  # noqa: PLR0915, PLR0912, C901
                 "shards_edge_balanced": sum(p.balanced for p in plans) if world > 1 else None,
                 "rank_edge_loads_first_batch": list(plans[0].loads) if world > 1 else None,
             },
+            "launch": ("eager" + capture_note) if not replay else f"hipgraph-replay ({n_sweeps} x {len(handles)}-step sweep graph + " + (f"one {n_rest}-step graph" if rest is not None else f"{n_rest} per-step graphs") + f"{', RCCL all-reduce captured' if pg is not None else ''})",
+            "final_loss": final_loss,
+            "full": bool(args.full),
+        }
+    if not args.full:
+        # a plain run ends here: the timed steps and the line they give
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if pg is not None:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return result
+
+    # --full: what takes runs of its own, after the timed steps.
+    # Dominant-kernel duration: the graph pass alone, args.steps launches over
+    # the resident mini-batches captured back to back in one HIP graph and
+    # timed with HIP events on the launch stream (no host launch overhead;
+    # agrees with the rocprofv3 kernel average, profiles/).
+    # (at least 200 launches: a graph of K launches also carries the graph's
+    # own launch latency, ~9 us, which at the driver's K = 20 would add ~0.45
+    # us to every launch's average; the rocprofv3 average is the cross-check)
+    n_kernel = max(args.steps, 200)
+    kernel_ms = None if layer_path else step.time_graph_pass(handles, n_kernel, global_batch=B * world)
+    if kernel_ms is None:  # layer path: no single graph-pass kernel; price the whole step
+        kernel_ms = elapsed / args.steps * 1e3
+    # the step split (pass / reduce + Adam / the rest: launch gaps inside the
+    # replayed graphs), world of one only
+    reduce_ms = None if (layer_path or pg is not None) else step.time_reduce(handles, n_kernel, global_batch=B * world)
+    if pg is not None:
+        km = torch.tensor([kernel_ms], dtype=torch.float64, device=dev)
+        torch.distributed.all_reduce(km, op=torch.distributed.ReduceOp.MAX)
+        kernel_ms = float(km.item())
+
+    s = 2 if args.dtype == "bf16" else 4
+    alg = float(np.mean([algorithmic_bytes(packed, h.gids_host, args.model, s) for h in handles]))
+    design = float(np.mean([design_bytes(packed, h.gids_host, args.model) for h in handles]))
+    n_params = sum(p.numel() for p in model.parameters())
+    adam_bytes = 28 * n_params  # Adam fp32: read param, grad, m, v; write param, m, v (§8(d))
+    kernel_alg = alg
+    achieved = kernel_alg / (kernel_ms * 1e-3) / 1e9
+    wall_gbs = (alg + adam_bytes) / (ms_step * 1e-3) / 1e9
+    pmc_cfg = default_cfg or (args.model in ("foutnet", "sgat", "vanilla", "ginet_nocluster") and args.graphs == "residue" and B == B_PER_GPU and args.dtype == "f32")
+    traffic, traffic_src = pmc_traffic_bytes(args.model) if pmc_cfg else (None, None)
+    large = args.model == "ginet" and (bool(args.force_large) or args.ginet_path != "auto" or args.dtype == "bf16" or any(h.lds((step.spec.entry, 1), lambda *sz: 0) > 160 * 1024 for h in handles))
+    # multi-kernel graph passes (Vanilla pipeline, GINet tile + tail kernels):
+    # the per-kernel PMC table of the same workload (tools/pmc_run.py <model>_<graphs>[_bf16])
+    if traffic is None and B == B_PER_GPU_FOR.get(args.graphs) and not args.force_large and args.ginet_path == "auto" and (
+        (args.model == "vanilla" and args.graphs in ("atom", "mixed")) or (args.model == "ginet" and args.graphs in ("atom", "mixed"))
+    ):
+        traffic, traffic_src = pmc_traffic_step(args.model, args.graphs, args.dtype)
+    copy_gbs = None if args.no_stream_copy else stream_copy_gbs(dev)
+    # §8(d) FLOP side: algorithmic FLOPs per launch against the dense MFMA peak
+    # of the compute dtype, and MFMA utilisation from the committed PMC pass
+    flops = float(np.mean([algorithmic_flops(packed, h.gids_host, args.model) for h in handles]))
+    tflops = flops / (kernel_ms * 1e-3) / 1e12
+    n_wg = B
+    if args.model == "vanilla" and not layer_path:
+        from deeprank2_amd.neuralnets.gnn.vanilla_gnn import split_k  # noqa: PLC0415
+
+        n_wg = B * split_k(handles[0], 30, 3)
+    mfma = pmc_mfma(args.model, kernel_ms, n_wg) if pmc_cfg else None
+
+    if rank == 0:
+        cpu = None
+        if world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(graphs[:B], model_name=args.model)
+        kname = "layer-level path (FoutLayer/SGAT/GINetConvLayer + pooling kernels, torch autograd): whole-step wall clock" if layer_path else {"ginet": "ginet_large_conv1_kernel + ginet_large_tail_kernel (dr_ginet_large_pass)" if large else ((f"ginet_acc_kernel (dr_ginet_acc_pass: {step._acc_rows(handles[0])} workgroups, each runs every R-th graph's fwd+loss+bwd and sums its gradients on chip; one partial row per workgroup)" if step._acc_rows(handles[0]) else "ginet_graph_kernel (dr_ginet_graph_pass, fwd+loss+bwd, 1 workgroup/graph)")), "foutnet": "fout_graph_kernel<false> (dr_fout_graph_pass)", "vanilla": "vanilla_graph_kernel (dr_vanilla_fused_pass) / vanilla pipeline (dr_vanilla_graph_pass)", "sgat": "fout_graph_kernel<true> (dr_sgat_graph_pass)", "ginet_nocluster": "ginet_nocluster_kernel (dr_ginet_nocluster_graph_pass)"}[args.model]
+        result.update({
             "roofline": {
                 "kernel": kname,
                 "bound": "hbm",
@@ -924,10 +1002,8 @@ def main(args):  # noqa: PLR0915, PLR0912, C901
                 "wallclock": {"bytes_per_step": int(alg + adam_bytes), "achieved": round(wall_gbs, 2), "frac": round(wall_gbs / HBM_PEAK_GBS, 5), "note": "B_alg(step) = sum_g B_alg(g) + 28*P (Adam fp32) over ms_per_step"},
             },
             "step_split_us": None if reduce_ms is None else {"graph_pass": round(kernel_ms * 1e3, 2), "reduce_adam": round(reduce_ms * 1e3, 2), "other": round(ms_step * 1e3 - (kernel_ms + reduce_ms) * 1e3, 2), "note": "graph pass and dr_reduce_update each timed alone (HIP events around a HIP graph of max(--steps, 200) launches); other = ms_per_step minus both: the gaps between launches in the replayed step graphs"},
-            "launch": ("eager" + capture_note) if captured is None else f"hipgraph-replay ({n_sweeps} x {len(handles)}-step sweep graph + " + (f"one {n_rest}-step graph" if rest is not None else f"{n_rest} per-step graphs") + f"{', RCCL all-reduce captured' if pg is not None else ''})",
             "cpu_baseline": cpu,
-            "final_loss": float(loss.item()),
-        }
+        })
         print(json.dumps(result), flush=True)
     if pg is not None:
         torch.distributed.barrier()

@@ -58,13 +58,13 @@ for S in "$@"; do
       timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 240 --timeout-method thread -k "${S#test:}" > $O/pytest_k.log 2>&1 || { grep -E "^E |FAILED|Error" $O/pytest_k.log | head -30; fail pytest-k; }
       grep -E "PASSED|SKIPPED" $O/pytest_k.log | cut -c1-150; tail -1 $O/pytest_k.log ;;
     bench)
-      timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; fail bench; }
+      timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail $O/bench_default.err; fail bench; }
       js $O/bench_default.json ;;
     driver)
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_steps.json 2> $O/bench_driver_steps.err || { tail $O/bench_driver_steps.err; fail driver; }
+      timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_driver_steps.json 2> $O/bench_driver_steps.err || { tail $O/bench_driver_steps.err; fail driver; }
       js $O/bench_driver_steps.json ;;
     rocprof)
-      (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/kt_headline -o run -- python3 $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline > $O/kt_headline.log 2>&1) || fail rocprof
+      (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/kt_headline -o run -- python3 $R/bench.py --steps 200 --warmup 20 > $O/kt_headline.log 2>&1) || fail rocprof
       f=$(find $O/kt_headline -name "*kernel_stats.csv" | head -1); cp "$f" $O/rocprof_kernel_stats_headline.csv; cut -d, -f1-8 $O/rocprof_kernel_stats_headline.csv | head -6 ;;
     stamps)
       DR_LIB_NAME=libdeeprank2_amd_stamps.so timeout -k 10 200 python tools/stamp_profile.py 64 > $O/stamps_ginet_graph_kernel.txt 2>&1 || fail stamps
@@ -92,7 +92,7 @@ for S in "$@"; do
     configs)
       : > $O/bench_configs.jsonl
       for cfg in "--model foutnet --graphs residue" "--model ginet --graphs atom" "--model ginet --graphs atom --dtype bf16" "--model ginet --graphs mixed" "--model vanilla --graphs mixed" "--model vanilla --graphs atom" "--model vanilla --graphs residue" "--model sgat --graphs residue" "--model ginet_nocluster --graphs residue"; do
-        timeout -k 10 400 python bench.py --steps 100 --warmup 10 $cfg > $O/cfg.log 2>&1 || { tail -5 $O/cfg.log; fail "$cfg"; }
+        timeout -k 10 400 python bench.py --full --steps 100 --warmup 10 $cfg > $O/cfg.log 2>&1 || { tail -5 $O/cfg.log; fail "$cfg"; }
         grep '^{' $O/cfg.log | tail -1 >> $O/bench_configs.jsonl
         echo "$cfg | $(js $O/cfg.log)"
       done ;;
@@ -100,7 +100,7 @@ for S in "$@"; do
       : > $O/batch_sweep_ginet.jsonl
       for B in 64 256 1024 4096 16384; do
         nb=4; [ $B -ge 4096 ] && nb=2; [ $B -ge 16384 ] && nb=1
-        timeout -k 10 400 python bench.py --batch $B --batches $nb --steps 20 --warmup 3 --no-cpu-baseline --no-stream-copy > $O/sweep.log 2>&1 || { tail -5 $O/sweep.log; fail "sweep B=$B"; }
+        timeout -k 10 400 python bench.py --full --batch $B --batches $nb --steps 20 --warmup 3 --no-cpu-baseline --no-stream-copy > $O/sweep.log 2>&1 || { tail -5 $O/sweep.log; fail "sweep B=$B"; }
         grep '^{' $O/sweep.log | tail -1 >> $O/batch_sweep_ginet.jsonl; echo "B=$B | $(js $O/sweep.log)"
       done ;;
     trainer)
@@ -114,7 +114,7 @@ for S in "$@"; do
       : > $O/ab.txt
       for v in "${order[@]}"; do
         lib=libdeeprank2_amd.so; [ "$v" = main ] || lib=libdeeprank2_amd_$v.so
-        DR_LIB_NAME=$lib timeout -k 10 300 python bench.py --steps ${AB_STEPS:-200} --warmup 20 --no-cpu-baseline --no-stream-copy $AB_ARGS > $O/ab_$v.json 2> $O/ab_$v.err || { tail -5 $O/ab_$v.err; fail "ab $v"; }
+        DR_LIB_NAME=$lib timeout -k 10 300 python bench.py --full --steps ${AB_STEPS:-200} --warmup 20 --no-cpu-baseline --no-stream-copy $AB_ARGS > $O/ab_$v.json 2> $O/ab_$v.err || { tail -5 $O/ab_$v.err; fail "ab $v"; }
         echo "$v | $(js $O/ab_$v.json)" | tee -a $O/ab.txt
       done ;;
     timeline)

@@ -2,10 +2,93 @@
 
 from __future__ import annotations
 
+import atexit
+import gzip
+import json
+import os
+import shutil
+import tempfile
+
 import numpy as np
 import torch
 
 from oracle import pyg_ops as P
+
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+_h5_dir = None
+_pretrained = None
+
+
+def golden_hdf5_dir():
+    """DeepRank2's own test files (``tests/golden/hdf5/*.hdf5.gz``, stored by
+    ``tests/golden/make_hdf5_fixtures.py``) unpacked once per process into a
+    temporary directory; returns that directory."""
+    global _h5_dir  # noqa: PLW0603
+    if _h5_dir is None:
+        d = tempfile.mkdtemp(prefix="golden_hdf5_")
+        atexit.register(shutil.rmtree, d, ignore_errors=True)
+        src = os.path.join(GOLDEN, "hdf5")
+        for name in sorted(os.listdir(src)):
+            if name.endswith(".hdf5.gz"):
+                with gzip.open(os.path.join(src, name), "rb") as f, open(os.path.join(d, name[: -len(".gz")]), "wb") as g:
+                    shutil.copyfileobj(f, g)
+        _h5_dir = d
+    return _h5_dir
+
+
+def golden_pretrained():
+    """DeepRank2's pre-trained VanillaNetwork checkpoint, written once per
+    process in the reference's format (``Trainer._save_model``: ``torch.save``
+    with dill) from its stored data (``tests/golden/pretrained``: tensors in
+    the ``.npz``, everything else in the ``.json``); returns the file's path.
+
+    As in the reference's file, live objects stand beside the data: the
+    dataset class and the optimizer's class pickled by value (dill's
+    ``_create_type``; the classes here are local stand-ins of the same names),
+    an optimizer instance carrying the stored state, a loss-function instance,
+    and numpy scalars for the means / devs — so ``torch.load(weights_only=True)``
+    refuses the file and ``io.checkpoint``'s opcode reader has to read it."""
+    global _pretrained  # noqa: PLW0603
+    if _pretrained is not None:
+        return _pretrained
+    import dill  # noqa: PLC0415
+
+    stem = os.path.join(GOLDEN, "pretrained", "testing_graph_model")
+    with open(stem + ".json") as f:
+        state = json.load(f)
+    with np.load(stem + ".npz", allow_pickle=False) as z:
+        tensors = {k: torch.from_numpy(z[k]) for k in z.files}
+    model_state = {k.split("/", 1)[1]: v for k, v in tensors.items() if k.startswith("model_state/")}
+    opt_state = {}
+    for k, v in tensors.items():
+        if k.startswith("optimizer_state/"):
+            _, i, name = k.split("/")
+            opt_state.setdefault(int(i), {})[name] = v
+    groups = state.pop("param_groups")
+    for g in groups:
+        g["betas"] = tuple(g["betas"])
+    state["classes_to_index"] = {k: v for k, v in state["classes_to_index"]}
+    state["means"] = {k: np.float64(v) for k, v in state["means"].items()}
+    state["devs"] = {k: np.float64(v) for k, v in state["devs"].items()}
+    # classes of module __main__ that no module holds: dill pickles them by value
+    adam = type(state["optimizer"], (torch.optim.Adam,), {"__module__": "__main__"})
+    assert state["lossfunction"] == "CrossEntropyLoss"
+    optimizer = adam([torch.nn.Parameter(v.clone()) for v in model_state.values()], lr=state["lr"], weight_decay=state["weight_decay"])
+    optimizer.load_state_dict({"state": opt_state, "param_groups": groups})
+    state.update(
+        data_type=type(state["data_type"], (), {"__module__": "__main__"}),
+        model_state=model_state,
+        optimizer=optimizer,
+        optimizer_state={"state": opt_state, "param_groups": groups},
+        lossfunction=torch.nn.CrossEntropyLoss(),
+    )
+    d = tempfile.mkdtemp(prefix="golden_pretrained_")
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+    path = os.path.join(d, "testing_graph_model.pth.tar")
+    torch.save(state, path, pickle_module=dill)
+    _pretrained = path
+    return path
 
 
 def golden_batch(z):

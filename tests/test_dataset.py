@@ -3,29 +3,31 @@
 * Synthetic DeepRank2-layout HDF5 files written by ``utils.synthetic`` (our own
   writer): items and collated batches equal the generator's arrays, edges
   doubled as ``dataset.py:944-948,994-996``.
-* The reference's own fixtures (``tests/data/hdf5``) read IN PLACE when
-  /root/reference is present (this container only; never copied into the
-  repo): batch tensors equal the ``ginet_1atn`` golden inputs, and the
+* The reference's own fixtures (``tests/data/hdf5``; their numeric datasets
+  are stored under ``tests/golden/hdf5``, see ``make_hdf5_fixtures.py``):
+  batch tensors equal the ``ginet_1atn`` golden inputs, and the
   assertions of the reference's ``tests/test_dataset.py`` (lengths, target
   filter, doubled edge feature statistics, task/classes) hold.
 """
 
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import pytest
 import torch
+from _util import golden_hdf5_dir
 
 from deeprank2_amd.data import Batch, collate
 from deeprank2_amd.dataset import GraphDataset
 from deeprank2_amd.loader import DataLoader
 from deeprank2_amd.utils import synthetic as S
 
-REF_H5 = "/root/reference/tests/data/hdf5"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF_H5), reason="reference fixtures not present (GPU box)")
 DEFAULT_FEATURES = ["res_type", "polarity", "bsa", "res_depth", "hse", "info_content", "pssm"]  # reference tests/test_trainer.py:31-39
+
+
+@pytest.fixture(scope="module")
+def ref_h5():
+    return golden_hdf5_dir()
 
 
 @pytest.fixture(scope="module")
@@ -178,22 +180,20 @@ def test_collate_free_standing_batch():
     assert torch.equal(b.edge_index, c["edge_index"]) and b.num_graphs == 2
 
 
-# ---- the reference's fixtures, read in place -------------------------------
+# ---- the reference's fixtures (tests/golden/hdf5) --------------------------
 
 
-@needs_ref
-def test_1atn_batch_equals_golden_inputs(golden):
+def test_1atn_batch_equals_golden_inputs(golden, ref_h5):
     z = golden("ginet_1atn")
-    ds = GraphDataset(f"{REF_H5}/1ATN_ppi.hdf5", node_features=DEFAULT_FEATURES, edge_features=["distance"], target="irmsd", clustering_method="mcl")
+    ds = GraphDataset(f"{ref_h5}/1ATN_ppi.hdf5", node_features=DEFAULT_FEATURES, edge_features=["distance"], target="irmsd", clustering_method="mcl")
     b = next(iter(DataLoader(ds, batch_size=4)))
     for k in ("x", "edge_index", "edge_attr", "batch", "cluster0", "cluster1", "y"):
         np.testing.assert_array_equal(getattr(b, k).numpy(), z[f"in/{k}"], err_msg=k)
 
 
-@needs_ref
-def test_reference_dataset_assertions():
+def test_reference_dataset_assertions(ref_h5):
     """Reference tests/test_dataset.py:178-197, 348-368, 520-550."""
-    p = f"{REF_H5}/1ATN_ppi.hdf5"
+    p = f"{ref_h5}/1ATN_ppi.hdf5"
     ds = GraphDataset(p, node_features=DEFAULT_FEATURES, edge_features=["distance"], target="irmsd")
     assert len(ds) == 4 and ds[0] is not None
     with pytest.raises(IndexError):
@@ -209,10 +209,9 @@ def test_reference_dataset_assertions():
     assert ds.task == "classif" and ds.classes == [0, 1]
 
 
-@needs_ref
-def test_test_hdf5_matches_foutnet_golden_inputs(golden):
+def test_test_hdf5_matches_foutnet_golden_inputs(golden, ref_h5):
     z = golden("foutnet_testhdf5")
-    ds = GraphDataset(f"{REF_H5}/test.hdf5", node_features=DEFAULT_FEATURES, edge_features=["distance"], target="binary", clustering_method="mcl")
+    ds = GraphDataset(f"{ref_h5}/test.hdf5", node_features=DEFAULT_FEATURES, edge_features=["distance"], target="binary", clustering_method="mcl")
     b = next(iter(DataLoader(ds, batch_size=len(ds))))
     for k in ("x", "edge_index", "cluster0", "cluster1"):
         np.testing.assert_array_equal(getattr(b, k).numpy(), z[f"in/{k}"], err_msg=k)

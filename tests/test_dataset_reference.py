@@ -1,6 +1,9 @@
 """The reference's GraphDataset tests (``tests/test_dataset.py:582-1260`` of
-DeepRank2) restated against the fixtures the reference ships, read in place
-(CPU; skipped where ``/root/reference`` is absent, e.g. on the GPU box).
+DeepRank2) restated against the fixtures the reference ships (CPU; their
+numeric datasets are stored under ``tests/golden/hdf5``, the data of its
+pre-trained checkpoint under ``tests/golden/pretrained``, from which
+``_util.golden_pretrained`` writes a checkpoint in the reference's format:
+``make_hdf5_fixtures.py``).
 
 The reference runs its transform / standardisation tests on
 ``tests/data/hdf5/train.hdf5``, which its repository does not hold; they run
@@ -17,17 +20,22 @@ transform or standardisation applies, inheritance from ``train_source``,
 
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import pytest
+from _util import golden_hdf5_dir, golden_pretrained
 
 from deeprank2_amd.dataset import GraphDataset
 from deeprank2_amd.io.hdf5 import read_files
 
-REF_H5 = "/root/reference/tests/data/hdf5"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_H5), reason="reference fixtures not present (GPU box)")
-H5 = f"{REF_H5}/test.hdf5"
+REF_H5 = H5 = PRETRAINED = None  # set by _fixtures when a test of this module runs
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _fixtures():
+    global REF_H5, H5, PRETRAINED  # noqa: PLW0603
+    REF_H5 = golden_hdf5_dir()
+    H5 = f"{REF_H5}/test.hdf5"
+    PRETRAINED = golden_pretrained()
 
 
 def _raw(feat):
@@ -192,12 +200,10 @@ def test_invalid_train_source():
         GraphDataset(H5, train_source=3.0)
 
 
-PRETRAINED = "/root/reference/tests/data/pretrained/testing_graph_model.pth.tar"
-
-
 def test_reference_checkpoint_read_inert():
     """The reference's pre-trained VanillaNetwork checkpoint (it pickles the
-    optimizer class with dill) read by the opcode reader: nothing from the
+    optimizer class with dill; here written in that format from its stored
+    data) read by the opcode reader: nothing from the
     file runs; weights, optimizer state, standardisation and settings come out
     as data (reference tests/test_trainer.py:661-700 load it with torch.load)."""
     from deeprank2_amd.io.checkpoint import load_checkpoint, transform_from_source  # noqa: PLC0415

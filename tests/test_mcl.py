@@ -5,19 +5,16 @@ stored, and the host-side layout / pooling / assignment logic."""
 from __future__ import annotations
 
 import glob
-import os
 
 import numpy as np
 import pytest
 import torch
-from _util import golden_graphs
+from _util import golden_graphs, golden_hdf5_dir
 
 from deeprank2_amd import clustering
 from deeprank2_amd.utils import community_pooling as CP
 from oracle import mcl_ref
 from oracle import pyg_ops as P
-
-REF_H5 = "/root/reference/tests/data/hdf5"
 
 
 @pytest.mark.parametrize("name", ["ginet_1atn", "foutnet_testhdf5"])
@@ -30,12 +27,12 @@ def test_oracle_reproduces_stored_depth0_depth1(golden, name):
         np.testing.assert_array_equal(mcl_ref.mcl_community_detection(pe, k), c1)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_H5), reason="reference fixtures not present")
 def test_oracle_reproduces_reference_hdf5_clusters():
-    """Every entry of the reference's fixtures that stores clustering/mcl."""
+    """Every entry of the reference's fixtures that stores clustering/mcl
+    (tests/golden/hdf5: 1ATN_ppi, test and variants do)."""
     from deeprank2_amd.io import hdf5  # noqa: PLC0415
 
-    files = sorted(glob.glob(f"{REF_H5}/*.hdf5"))
+    files = sorted(glob.glob(f"{golden_hdf5_dir()}/*.hdf5"))
     seen = 0
     for p, d in zip(files, hdf5.read_files(files)):
         if isinstance(d, Exception):
