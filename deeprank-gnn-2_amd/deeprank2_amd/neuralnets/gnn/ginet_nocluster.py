@@ -46,6 +46,9 @@ class _NcPlan:
         row0 = np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
         plan = vanilla_tile_plan(h, n, row0, NC_TILE, st.n_edge_feat, lds_check=False)
         if plan is None:
+            if h.store.edges_in(idx) == 0:  # no halo to stage: the tile kernels need one (dr_nc_plan.halo_max >= 1)
+                msg = "ginet_nocluster large-graph path: no graph of this batch has an edge, so there is no tile plan; such graphs fit the per-graph kernel (leave force_large off)"
+                raise RuntimeError(msg)
             msg = "ginet_nocluster large-graph path: no tile plan for this batch (a tile's halo exceeds 65535 nodes)"
             raise RuntimeError(msg)
         tensors, (n_tiles, hmax, emax, tmax) = plan

@@ -115,6 +115,15 @@ def _dense(ids, what):
     return inv.astype(np.int64), int(uniq.size)
 
 
+def _edge_attr_2d(edge_attr, n_edges):
+    """``edge_attr`` as float32 [E, Fe].  A graph without edges keeps its own
+    second dimension ([0, Fe]); ``reshape(0, -1)`` cannot infer one."""
+    ea = np.asarray(edge_attr, dtype=np.float32)
+    if ea.size == 0:
+        return ea.reshape(n_edges, ea.shape[1] if ea.ndim == 2 else 1)  # noqa: PLR2004
+    return ea.reshape(n_edges, -1)
+
+
 def pack_graphs(records: list[GraphRecord], require_clusters: bool = True, threads: int = 0) -> PackedGraphs:
     """Pack per-graph records into the store layout with the native host
     packer (``dr_pack_sizes`` / ``dr_pack_fill``, threads over graphs)."""
@@ -159,7 +168,7 @@ def pack_graphs(records: list[GraphRecord], require_clusters: bool = True, threa
             c1_off[gi + 1] = c1_off[gi] + len(c1)
         ys.append(np.nan if r.y is None else float(np.asarray(r.y).reshape(-1)[0]))
         if has_ea:
-            eas.append(np.asarray(r.edge_attr, dtype=np.float32).reshape(ei.shape[1], -1))
+            eas.append(_edge_attr_2d(r.edge_attr, ei.shape[1]))
     x = np.concatenate(xs) if G else np.zeros((0, F), np.float32)
     ei_all = np.ascontiguousarray(np.concatenate(eis, axis=1)) if G else np.zeros((2, 0), np.int64)
     ea_all = np.ascontiguousarray(np.concatenate(eas)) if has_ea else None

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from deeprank2_amd.store import PackedGraphs, _csr, _dense, _same_multiset
+from deeprank2_amd.store import PackedGraphs, _csr, _dense, _edge_attr_2d, _same_multiset
 
 
 def pack_graphs_numpy(records, require_clusters: bool = True) -> PackedGraphs:  # noqa: PLR0915, C901
@@ -54,7 +54,7 @@ def pack_graphs_numpy(records, require_clusters: bool = True) -> PackedGraphs:  
         trps.append(trp)
         tcols.append(tcs)
         if has_ea:
-            ea = np.asarray(r.edge_attr, dtype=np.float32).reshape(e, -1)
+            ea = _edge_attr_2d(r.edge_attr, e)
             eas.append(ea[perm])
 
         if r.cluster0 is None or r.cluster1 is None:
@@ -83,7 +83,7 @@ def pack_graphs_numpy(records, require_clusters: bool = True) -> PackedGraphs:  
         tkey = np.unique(pcol * k0 + prow)
         p1tps.append(np.searchsorted(key, (tkey % k0) * k0 + tkey // k0).astype(np.int32))
         if has_ea:  # PyG coalesce: attributes of merged edges summed in edge order
-            ea_in = np.asarray(r.edge_attr, dtype=np.float32).reshape(e, -1)
+            ea_in = _edge_attr_2d(r.edge_attr, e)
             pe = np.zeros((key.size, ea_in.shape[1]), np.float32)
             np.add.at(pe, np.searchsorted(key, pr[keep] * k0 + pc[keep]), ea_in[keep])
             p1eas.append(pe)
