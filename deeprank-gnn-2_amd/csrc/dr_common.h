@@ -3,13 +3,54 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <mutex>
+
+#include "../../include/deeprank2_amd.h"
 
 #define DR_CHECK(expr)                 \
   do {                                 \
     const int _e = (int)(expr);        \
     if (_e != 0) return _e;            \
   } while (0)
+
+// The regression losses of the graph passes beside MSE (DR_LOSS_L1 /
+// DR_LOSS_SMOOTH_L1 / DR_LOSS_HUBER; the reference's losstypes.py:3-8) on one
+// residual d = prediction - target, as torch computes them: *term the
+// unscaled per-graph loss term, *grad = d term / d d.  param: SmoothL1's beta
+// (0: L1) or Huber's delta.  At a NaN residual the term is NaN and the
+// gradient is NaN, except L1's, which is 0 (sign(NaN) = 0 in torch).
+__device__ __forceinline__ void dr_regress_loss(int kind, float param, float d, float* term, float* grad) {
+  const float ad = fabsf(d);
+  if (kind == DR_LOSS_L1 || (kind == DR_LOSS_SMOOTH_L1 && param == 0.f)) {
+    *term = ad;
+    *grad = (d > 0.f ? 1.f : 0.f) - (d < 0.f ? 1.f : 0.f);
+  } else if (kind == DR_LOSS_SMOOTH_L1) {
+    *term = ad < param ? 0.5f * d * d / param : ad - 0.5f * param;
+    *grad = d < -param ? -1.f : d > param ? 1.f : d / param;
+  } else {  // DR_LOSS_HUBER
+    *term = ad < param ? 0.5f * d * d : param * (ad - 0.5f * param);
+    *grad = d < -param ? -param : d > param ? param : d;
+  }
+}
+
+// Host: dr_pass.loss_kind / loss_param are ones the kernels know (every
+// graph-pass entry checks this before its first HIP call).
+inline int dr_check_loss(const dr_pass* p) {
+  switch (p->loss_kind) {
+    case DR_LOSS_NONE:
+    case DR_LOSS_MSE:
+    case DR_LOSS_CE:
+    case DR_LOSS_L1:
+      return DR_OK;
+    case DR_LOSS_SMOOTH_L1:
+      return (std::isfinite(p->loss_param) && p->loss_param >= 0.f) ? DR_OK : DR_E_ARG;
+    case DR_LOSS_HUBER:
+      return (std::isfinite(p->loss_param) && p->loss_param > 0.f) ? DR_OK : DR_E_ARG;
+    default:
+      return DR_E_ARG;
+  }
+}
 
 // Sum over the 64 lanes of a wave (butterfly; every lane gets the total).
 __device__ __forceinline__ float dr_wave_sum(float v) {

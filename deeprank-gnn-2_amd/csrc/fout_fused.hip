@@ -391,6 +391,12 @@ __device__ __forceinline__ void fout_tail(const dr_pass& p, const FoutTail t, in
       const float wy = p.class_w ? p.class_w[yi] : 1.f;
       if (p.loss_per_graph) p.loss_per_graph[b] = wy * (lse - t.Dout[yi]);
       for (int q = 0; q < OUT; ++q) t.Dout[q] = wy * (expf(t.Dout[q] - lse) - (q == yi ? 1.f : 0.f)) * p.loss_scale;
+    } else if (p.loss_kind != DR_LOSS_NONE) {  // L1 / SmoothL1 / Huber on column 0
+      float term, gd;
+      dr_regress_loss(p.loss_kind, p.loss_param, t.Dout[0] - y_g, &term, &gd);
+      if (p.loss_per_graph) p.loss_per_graph[b] = term;
+      t.Dout[0] = gd * p.loss_scale;
+      for (int q = 1; q < OUT; ++q) t.Dout[q] = 0.f;
     } else {
       for (int q = 0; q < OUT; ++q) t.Dout[q] = p.dout[(int64_t)b * OUT + q];
     }
@@ -1241,6 +1247,7 @@ namespace {
 int fout_family_pass(bool sg, const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
                      const dr_fout_weights* w, const dr_pass* pass, int32_t lds_bytes, void* stream) {
   if (!store || !descs || !w || !pass || n_batch < 0) return DR_E_ARG;
+  DR_CHECK(dr_check_loss(pass));
   if (sg && (store->n_edge_feat != 1 || !store->ea || !store->p1_ea || !store->p1t_pid)) return DR_E_UNSUPPORTED;
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
   if (store->n_feat < 1 || 2 * 16 * store->n_feat + 1072 + 2112 + 65 * pass->out_dim > 6 * NT) return DR_E_UNSUPPORTED;
@@ -1304,6 +1311,7 @@ int fout_large_family(bool sg, const dr_graph_store* store, const dr_graph_desc*
                       const dr_large_plan* plan, const dr_fout_weights* w, const dr_pass* pass, int32_t z_stride,
                       int32_t conv_lds_bytes, int32_t tail_lds_bytes, void* stream) {
   if (!store || !descs || !w || !pass || !plan || n_batch < 0) return DR_E_ARG;
+  DR_CHECK(dr_check_loss(pass));
   if (sg && (store->n_edge_feat != 1 || !store->ea || !store->p1_ea || !store->p1t_pid)) return DR_E_UNSUPPORTED;
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
   if (store->n_feat < 1 || store->n_feat > 64) return DR_E_UNSUPPORTED;

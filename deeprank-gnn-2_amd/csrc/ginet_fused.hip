@@ -1966,6 +1966,7 @@ extern "C" int dr_ginet_graph_pass(const dr_graph_store* store, const dr_graph_d
                                    const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes,
                                    void* stream) {
   if (!store || !descs || !w || !pass || n_batch < 0) return DR_E_ARG;
+  DR_CHECK(dr_check_loss(pass));
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
   if (store->n_feat < 1 || 32 * store->n_feat > 2 * NT) return DR_E_UNSUPPORTED;  // F <= 64
   if (lds_bytes > 160 * 1024) return DR_E_LDS;
@@ -2012,6 +2013,7 @@ extern "C" int dr_ginet_acc_pass(const dr_graph_store* store, const dr_graph_des
                                  const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes, int32_t n_groups,
                                  const int32_t* plan, const int32_t* max_sizes, void* stream) {
   if (!store || !descs || !w || !pass || n_batch < 0 || n_groups < 1) return DR_E_ARG;
+  DR_CHECK(dr_check_loss(pass));
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
   if (store->n_feat < 1 || 32 * store->n_feat > 2 * NT) return DR_E_UNSUPPORTED;  // F <= 64
   if (pass->compute_dtype != DR_DTYPE_F32) return DR_E_UNSUPPORTED;
@@ -2076,6 +2078,7 @@ extern "C" int dr_ginet_large_pass(const dr_graph_store* store, const dr_graph_d
                                    const dr_large_plan* plan, const dr_ginet_weights* w, const dr_pass* pass,
                                    int32_t conv_lds_bytes, int32_t tail_lds_bytes, void* stream) {
   if (!store || !descs || !w || !pass || !plan || n_batch < 0) return DR_E_ARG;
+  DR_CHECK(dr_check_loss(pass));
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
   if (store->n_feat < 1 || store->n_feat > 64) return DR_E_UNSUPPORTED;
   if (conv_lds_bytes > 160 * 1024 || tail_lds_bytes > 160 * 1024) return DR_E_LDS;

@@ -149,6 +149,13 @@ __device__ __forceinline__ bool ginet_head(const dr_pass& p, const GinetHeadLds&
         if (ACC) t.acc[128 + 128 * OUT + OUT] += wy * (lse - t.dout[yi]);
         else if (p.loss_per_graph) st_part<WT>(p.loss_per_graph + pb, wy * (lse - t.dout[yi]));
         for (int q = 0; q < OUT; ++q) t.dout[q] = wy * (expf(t.dout[q] - lse) - (q == yi ? 1.f : 0.f)) * p.loss_scale;
+      } else if (p.loss_kind != DR_LOSS_NONE) {  // L1 / SmoothL1 / Huber on column 0, as MSE
+        float term, gd;
+        dr_regress_loss(p.loss_kind, p.loss_param, t.dout[0] - y_g, &term, &gd);
+        if (ACC) t.acc[128 + 128 * OUT + OUT] += term;
+        else if (p.loss_per_graph) st_part<WT>(p.loss_per_graph + pb, term);
+        t.dout[0] = gd * p.loss_scale;
+        for (int q = 1; q < OUT; ++q) t.dout[q] = 0.f;
       } else {
         for (int q = 0; q < OUT; ++q) t.dout[q] = p.dout[(int64_t)b * OUT + q];
       }

@@ -867,6 +867,7 @@ extern "C" int dr_ginet_nocluster_graph_pass(const dr_graph_store* store, const 
                                              const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes,
                                              void* stream) {
   if (!store || !descs || !w || !pass || n_batch < 0) return DR_E_ARG;
+  DR_CHECK(dr_check_loss(pass));
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
   if (store->n_feat < 1 || 32 * store->n_feat > 2 * NT) return DR_E_UNSUPPORTED;  // F <= 64
   if (lds_bytes > 160 * 1024) return DR_E_LDS;
@@ -902,6 +903,7 @@ extern "C" int dr_ginet_nocluster_large_pass(const dr_graph_store* store, const 
                                              const dr_nc_plan* plan, const dr_ginet_weights* w, const dr_pass* pass,
                                              void* stream) {
   if (!store || !descs || !w || !pass || !plan || n_batch < 0) return DR_E_ARG;
+  DR_CHECK(dr_check_loss(pass));
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
   if (store->n_feat < 1 || store->n_feat > 64 || pass->compute_dtype != DR_DTYPE_F32) return DR_E_UNSUPPORTED;
   if (!plan->base || !plan->row0 || !plan->row_slot || !plan->tile_row0 || !plan->tile_first || !plan->halo_off ||

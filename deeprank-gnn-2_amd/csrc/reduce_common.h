@@ -53,7 +53,8 @@ struct alignas(64) ReduceHdr {
   const uint32_t* fault;  // dr_adam.fault: nonzero -> NaN loss / gradients, no update
   int32_t B, slab_stride, head_stride, adam_enabled;
   float loss_scale, pad0;
-  float lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2_sqrt, pad1;
+  float lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2_sqrt;
+  float wd_mul;  // 1 - lr * weight_decay (AdamW's decoupled decay factor)
   float log2_beta1, log2_beta2;  // beta^t = exp2(t log2 beta): one v_exp_f32, not powf
   int32_t n_params, n_blocks;
   int16_t blk0[DR_MAX_PARAMS + 1];  // first block of each parameter (prefix sums of ceil(numel / RP)), blk0[n_params] = n_blocks
@@ -62,6 +63,9 @@ struct alignas(64) ReduceHdr {
   const int4* mirror_idx;
   uint32_t* fault_clear;    // dr_adam.fault_clear / ticket (stand-alone reduce kernel only)
   uint32_t* ticket;
+  // dr_optim.om_beta1 / om_beta2 (the rules of reduce_optim.hip; the Adam
+  // kernel forms 1.f - beta itself, as it always has)
+  float om_beta1, om_beta2;
 };
 
 typedef __attribute__((address_space(1))) unsigned int gu32r;
@@ -109,7 +113,9 @@ __device__ __forceinline__ float ld_part(const float* p) {
 // reduce-at-start GINet step, ginet_fused.hip).
 // row_off: the partials of graph b sit at row row_off + b (slab: (row_off + b)
 // * slab_rows): the half of the pipelined step's double buffer.
-template <int LD, bool LEAN = false, bool WTP = false>
+// OPT: the update rule (DR_OPT_*), fixed at compile time: the Adam
+// instantiation carries no branch for the others (reduce_optim.hip has them).
+template <int LD, bool LEAN = false, bool WTP = false, int OPT = DR_OPT_ADAM>
 __device__ __forceinline__ void reduce_block(const ReduceHdr& h, const ParamRec& r, int elem_block, bool first, int t,
                                              float (*part)[RP], int64_t tstep, int64_t row_off = 0) {
   // LEAN: partials always given, Adam always on (the one-launch step): the
@@ -220,17 +226,41 @@ __device__ __forceinline__ void reduce_block(const ReduceHdr& h, const ParamRec&
       bc2s = sqrtf(1.f - exp2f((float)tstep * h.log2_beta2));
       if (!LEAN && first && lp == 0) h.step_counter[0] = tstep;  // LEAN: the caller advances it
     }
-    float gr = gsum;
-    if (h.weight_decay != 0.f) gr = fmaf(h.weight_decay, p0, gr);
-    // torch.optim.Adam: exp_avg.lerp_(g, 1-b1); exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
     // every product-sum spelled out (fmaf / __fmul_rn / __fadd_rn): contraction
     // is then the same in every kernel that inlines this block
-    const float mv = fmaf(1.f - h.beta1, __fsub_rn(gr, m0), m0);
-    const float vv = fmaf(__fmul_rn(1.f - h.beta2, gr), gr, __fmul_rn(v0, h.beta2));
+    float gr = gsum, pb = p0;  // the gradient and the parameter the rule starts from
+    if constexpr (OPT == DR_OPT_ADAMW) {
+      // torch.optim.AdamW (_single_tensor_adam, decoupled_weight_decay):
+      // param.mul_(1 - lr*wd), the factor formed on the host in double as
+      // Python forms it; the moments then see the raw gradient
+      pb = __fmul_rn(p0, h.wd_mul);
+    } else {
+      if (h.weight_decay != 0.f) gr = fmaf(h.weight_decay, p0, gr);
+    }
+    // 1 - beta: Adam's own fp32 complement, or the caller's (dr_optim)
+    const float ob1 = OPT == DR_OPT_ADAM ? 1.f - h.beta1 : h.om_beta1;
+    const float ob2 = OPT == DR_OPT_ADAM ? 1.f - h.beta2 : h.om_beta2;
+    // exp_avg.lerp_(g, 1-b1)
+    const float mv = fmaf(ob1, __fsub_rn(gr, m0), m0);
     r.m[e] = mv;
-    r.v[e] = vv;
-    const float denom = __fadd_rn(__fdiv_rn(sqrtf(vv), bc2s), h.eps);
-    const float pn = fmaf(-(h.lr / bc1), __fdiv_rn(mv, denom), p0);
+    float pn;
+    if constexpr (OPT == DR_OPT_ADAMAX) {
+      // torch.optim.Adamax (_single_tensor_adamax): exp_inf = maximum(exp_inf*b2,
+      // |g| + eps), NaN propagating (fmaxf alone would drop it);
+      // param.addcdiv_(exp_avg, exp_inf, -lr / (1 - b1^t)).  r.v is the
+      // table's exp_avg_sq slot, carrying exp_inf.
+      const float ua = __fmul_rn(v0, h.beta2), ub = __fadd_rn(fabsf(gr), h.eps);
+      const float uv = (ua != ua || ub != ub) ? __builtin_nanf("") : fmaxf(ua, ub);
+      r.v[e] = uv;
+      pn = fmaf(-(h.lr / bc1), __fdiv_rn(mv, uv), pb);
+    } else {
+      // torch.optim.Adam / AdamW: exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
+      static_assert(OPT == DR_OPT_ADAM || OPT == DR_OPT_ADAMW, "unknown update rule");
+      const float vv = fmaf(__fmul_rn(ob2, gr), gr, __fmul_rn(v0, h.beta2));
+      r.v[e] = vv;
+      const float denom = __fadd_rn(__fdiv_rn(sqrtf(vv), bc2s), h.eps);
+      pn = fmaf(-(h.lr / bc1), __fdiv_rn(mv, denom), pb);
+    }
     if (WTP) __hip_atomic_store((__attribute__((address_space(1))) unsigned int*)(r.param + e), __float_as_uint(pn), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else r.param[e] = pn;
     if (!LEAN && h.mirror) {
@@ -279,6 +309,7 @@ inline int build_reduce(const dr_param_table* t, const float* slab, const float*
   h.weight_decay = adam->weight_decay;
   h.bias_c1 = adam->bias_c1;
   h.bias_c2_sqrt = adam->bias_c2_sqrt;
+  h.wd_mul = (float)(1.0 - (double)adam->lr * (double)adam->weight_decay);
   h.log2_beta1 = (float)std::log2((double)adam->beta1);
   h.log2_beta2 = (float)std::log2((double)adam->beta2);
   if ((adam->mirror == nullptr) != (adam->mirror_idx == nullptr)) return DR_E_ARG;

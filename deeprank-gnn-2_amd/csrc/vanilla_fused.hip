@@ -664,6 +664,12 @@ __global__ void __launch_bounds__(HT) vb_head(VA a) {
       const float wy = a.p.class_w ? a.p.class_w[yi] : 1.f;
       if (a.p.loss_per_graph) a.p.loss_per_graph[row] = wy * (lse - sDout[yi]);
       for (int q = 0; q < OUT; ++q) sDout[q] = wy * (expf(sDout[q] - lse) - (q == yi ? 1.f : 0.f)) * a.p.loss_scale;
+    } else if (a.p.loss_kind != DR_LOSS_NONE) {  // L1 / SmoothL1 / Huber on column 0
+      float term, gd;
+      dr_regress_loss(a.p.loss_kind, a.p.loss_param, sDout[0] - y_g, &term, &gd);
+      if (a.p.loss_per_graph) a.p.loss_per_graph[row] = term;
+      sDout[0] = gd * a.p.loss_scale;
+      for (int q = 1; q < OUT; ++q) sDout[q] = 0.f;
     } else {
       for (int q = 0; q < OUT; ++q) sDout[q] = a.p.dout[(int64_t)row * OUT + q];
     }
@@ -2263,6 +2269,7 @@ extern "C" int dr_vanilla_graph_pass(const dr_graph_store* store, const dr_graph
                                      const dr_vanilla_scratch* scratch, int32_t lds_bytes, void* stream) {
   (void)lds_bytes;
   if (!store || !descs || !w || !pass || !scratch || n_batch < 0) return DR_E_ARG;
+  DR_CHECK(dr_check_loss(pass));
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
   if (store->n_feat < 1 || store->n_feat > 64 || store->n_edge_feat < 0 || store->n_edge_feat > MAXFE)
     return DR_E_UNSUPPORTED;

@@ -918,6 +918,12 @@ __global__ void __launch_bounds__(NT) vanilla_graph_kernel(VGArgs a) {
       const float wy = p.class_w ? p.class_w[yi] : 1.f;
       if (p.loss_per_graph && lead) p.loss_per_graph[row] = wy * (lse - sdout[yi]);
       for (int q = 0; q < OUT; ++q) sdout[q] = wy * (expf(sdout[q] - lse) - (q == yi ? 1.f : 0.f)) * p.loss_scale;
+    } else if (p.loss_kind != DR_LOSS_NONE) {  // L1 / SmoothL1 / Huber on column 0
+      float term, gd;
+      dr_regress_loss(p.loss_kind, p.loss_param, sdout[0] - y_g, &term, &gd);
+      if (p.loss_per_graph && lead) p.loss_per_graph[row] = term;
+      sdout[0] = gd * p.loss_scale;
+      for (int q = 1; q < OUT; ++q) sdout[q] = 0.f;
     } else {
       for (int q = 0; q < OUT; ++q) sdout[q] = p.dout[(int64_t)row * OUT + q];
     }
@@ -1113,6 +1119,7 @@ extern "C" int dr_vanilla_fused_pass(const dr_graph_store* store, const dr_graph
                                      const int64_t* scratch_off, int32_t split, uint32_t* sync, float* wpack,
                                      int32_t lds_bytes, void* stream) {
   if (!store || !descs || !w || !pass || n_batch < 0 || !wpack) return DR_E_ARG;
+  DR_CHECK(dr_check_loss(pass));
   if (split < 1 || split > MAXK || (split > 1 && !sync)) return DR_E_ARG;
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
   if (store->n_feat < 1 || store->n_feat > 32 || store->x_stride > 32 || store->n_edge_feat < 0 ||

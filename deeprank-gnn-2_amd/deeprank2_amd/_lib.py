@@ -19,6 +19,12 @@ DR_PASS_WPACK_CURRENT = 4
 DR_LOSS_NONE = 0
 DR_LOSS_MSE = 1
 DR_LOSS_CE = 2
+DR_LOSS_L1 = 3
+DR_LOSS_SMOOTH_L1 = 4
+DR_LOSS_HUBER = 5
+DR_OPT_ADAM = 0
+DR_OPT_ADAMW = 1
+DR_OPT_ADAMAX = 2
 DR_MAX_OUT = 16
 DR_DROPOUT_OFF = 0
 DR_DROPOUT_MASK = 1
@@ -173,7 +179,7 @@ class PassC(ctypes.Structure):
         ("step_counter", VP),
         ("fault", VP),
         ("spin_limit", ctypes.c_int32),
-        ("pad0", ctypes.c_int32),
+        ("loss_param", ctypes.c_float),
         ("slot", VP),
     ]
 
@@ -196,6 +202,10 @@ class AdamC(ctypes.Structure):
         ("fault_clear", VP),
         ("ticket", VP),
     ]
+
+
+class OptimC(ctypes.Structure):
+    _fields_ = [("adam", AdamC), ("kind", ctypes.c_int32), ("om_beta1", ctypes.c_float), ("om_beta2", ctypes.c_float), ("pad0", ctypes.c_int32)]
 
 
 class GradRecipeC(ctypes.Structure):
@@ -251,6 +261,7 @@ SIGNATURES = [
     ("dr_sgat_graph_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(FoutWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, VP]),
     ("dr_sgat_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 8),
     ("dr_reduce_update", ctypes.c_int, [ctypes.POINTER(ParamTableC), VP, VP, ctypes.c_int32, ctypes.POINTER(AdamC), VP, ctypes.c_float, VP, VP]),
+    ("dr_reduce_update_opt", ctypes.c_int, [ctypes.POINTER(ParamTableC), VP, VP, ctypes.c_int32, ctypes.POINTER(OptimC), VP, ctypes.c_float, VP, VP]),
     ("dr_csr_from_coo", ctypes.c_int, [VP, VP, ctypes.c_int64, ctypes.c_int32, VP, VP, VP, VP, VP]),
     ("dr_spmm_csr", ctypes.c_int, [VP, VP, VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, VP, VP]),
     ("dr_spmm_csr_w", ctypes.c_int, [VP, VP, VP, VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, VP, VP]),

@@ -8,7 +8,13 @@ for any model with a ``fused_spec`` (GINet, FoutNet).
    per-graph partials;
 2. ``dr_reduce_update``: sums the partials into every gradient and
    applies ``torch.optim.Adam`` (lr, betas, eps, L2 ``weight_decay`` as
-   ``Trainer.configure_optimizers`` sets them, trainer.py:401-428).
+   ``Trainer.configure_optimizers`` sets them, trainer.py:401-428); with
+   ``optimizer="adamw"`` / ``"adamax"`` the same launch through
+   ``dr_reduce_update_opt`` applies ``torch.optim.AdamW`` / ``Adamax``.
+
+The in-kernel loss is ``loss``: "mse" / "ce", or "l1" / "smooth_l1" / "huber"
+(``loss_param``: SmoothL1Loss's beta, HuberLoss's delta), the regression
+losses the reference accepts (deeprank2/domain/losstypes.py:3-8).
 
 The dropout offset and Adam's step number live in a device counter that the
 two kernels advance themselves, so a step's launch arguments are constant and
@@ -32,6 +38,55 @@ from deeprank2_amd import _lib, layered
 from deeprank2_amd.fused import BatchHandle, launch, param_table, slab_rows_for
 
 
+# FusedTrainStep's ``loss`` / ``optimizer`` names -> DR_LOSS_* / DR_OPT_*
+LOSS_KINDS = {"mse": _lib.DR_LOSS_MSE, "ce": _lib.DR_LOSS_CE, "l1": _lib.DR_LOSS_L1, "smooth_l1": _lib.DR_LOSS_SMOOTH_L1, "huber": _lib.DR_LOSS_HUBER}
+OPT_KINDS = {"adam": _lib.DR_OPT_ADAM, "adamw": _lib.DR_OPT_ADAMW, "adamax": _lib.DR_OPT_ADAMAX}
+# the torch optimizer each kind's state dict belongs to, and its second state array
+_TORCH_OPT = {"adam": (torch.optim.Adam, "exp_avg_sq"), "adamw": (torch.optim.AdamW, "exp_avg_sq"), "adamax": (torch.optim.Adamax, "exp_inf")}
+
+
+def build_optimizer_state_dict(kind, params, states, step, lr, betas, eps, weight_decay):
+    """The state dict ``_TORCH_OPT[kind]`` over ``params`` would hold after
+    ``step`` steps with moments ``states`` [(exp_avg, second array)] (Adamax's
+    second array is ``exp_inf``): loads into that torch class."""
+    cls, second = _TORCH_OPT[kind]
+    opt = cls(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+    if step > 0:
+        for p, (m, v) in zip(params, states):
+            opt.state[p] = {"step": torch.tensor(float(step)), "exp_avg": m.detach().clone(), second: v.detach().clone()}
+    return opt.state_dict()
+
+
+def read_optimizer_state_dict(kind, sd, states):
+    """Inverse of :func:`build_optimizer_state_dict` (also takes the torch
+    optimizer's own state dict): fills ``states`` and returns (step, lr, betas,
+    eps, weight_decay)."""
+    second = _TORCH_OPT[kind][1]
+    group = sd["param_groups"][0]
+    if len(group["params"]) != len(states) or group.get("amsgrad", False):
+        msg = "optimizer state does not match this model (or uses amsgrad)"
+        raise ValueError(msg)
+    if kind != "adamax" and bool(group.get("decoupled_weight_decay", kind == "adamw")) != (kind == "adamw"):
+        msg = f"optimizer state's decoupled_weight_decay does not match the '{kind}' update rule"
+        raise ValueError(msg)
+    st_all = sd.get("state", {})
+    steps = set()
+    for slot, (m, v) in zip(group["params"], states):
+        st = st_all.get(slot)
+        if st is None:
+            m.zero_()
+            v.zero_()
+            steps.add(0)
+            continue
+        m.copy_(st["exp_avg"])
+        v.copy_(st[second])
+        steps.add(int(float(st["step"])))
+    if len(steps) > 1:
+        msg = f"parameters are at different optimizer steps {sorted(steps)}"
+        raise ValueError(msg)
+    return (steps.pop() if steps else 0), group["lr"], tuple(group["betas"]), group["eps"], group["weight_decay"]
+
+
 class FusedTrainStep:
     # the accumulating pass's defaults for new step objects (instance
     # attributes acc / acc_groups override them; tests set these to drive the
@@ -39,7 +94,7 @@ class FusedTrainStep:
     acc_default = None
     acc_groups_default = None
 
-    def __init__(self, model, lr=1e-3, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8, loss="mse", class_weights=None, process_group=None, max_batch=64, compute_dtype="f32"):
+    def __init__(self, model, lr=1e-3, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8, loss="mse", class_weights=None, process_group=None, max_batch=64, compute_dtype="f32", optimizer="adam", loss_param=None):
         self.model = model
         if compute_dtype not in ("f32", "bf16"):
             msg = f"compute_dtype must be 'f32' or 'bf16' (got {compute_dtype!r})"
@@ -58,10 +113,19 @@ class FusedTrainStep:
         self.device = dev
         self.out_dim = model.output_shape
         self.lr, self.weight_decay, self.betas, self.eps = lr, weight_decay, betas, eps
-        if loss not in ("mse", "ce"):
-            msg = f"loss must be 'mse' or 'ce' (got {loss!r})"
+        if loss not in LOSS_KINDS:
+            msg = f"loss must be one of {sorted(LOSS_KINDS)} (got {loss!r})"
+            raise ValueError(msg)
+        if optimizer not in OPT_KINDS:
+            msg = f"optimizer must be one of {sorted(OPT_KINDS)} (got {optimizer!r})"
             raise ValueError(msg)
         self.loss = loss
+        self.optimizer = optimizer
+        # SmoothL1Loss's beta / HuberLoss's delta (torch's defaults: 1.0)
+        self.loss_param = float(1.0 if loss_param is None else loss_param) if loss in ("smooth_l1", "huber") else 0.0
+        if not (self.loss_param >= 0.0 and self.loss_param != float("inf")) or (loss == "huber" and self.loss_param == 0.0):
+            msg = f"loss_param must be a finite beta >= 0 (smooth_l1) or delta > 0 (huber) (got {loss_param!r})"
+            raise ValueError(msg)
         self.class_weights = None if class_weights is None else torch.as_tensor(class_weights, dtype=torch.float32, device=dev)
         # host copy, taken once: the per-batch weight sum never syncs with the device
         self._cw_host = None if class_weights is None else torch.as_tensor(class_weights, dtype=torch.float32).detach().cpu().numpy()
@@ -139,7 +203,8 @@ class FusedTrainStep:
         p = _lib.PassC()
         p.flags = _lib.DR_PASS_FORWARD | _lib.DR_PASS_BACKWARD
         p.out_dim = self.out_dim
-        p.loss_kind = _lib.DR_LOSS_MSE if self.loss == "mse" else _lib.DR_LOSS_CE
+        p.loss_kind = LOSS_KINDS[self.loss]
+        p.loss_param = self.loss_param
         if self.spec.dropout > 0 and self.model.dropout > 0:
             p.use_dropout = _lib.DR_DROPOUT_HASH
             p.drop_p = self.model.dropout
@@ -171,6 +236,18 @@ class FusedTrainStep:
         self._adam_off.fault = self.fault.data_ptr()
         self._adam_div = _lib.AdamC.from_buffer_copy(a)
         self._adam_div.grad_div = self.wsum.data_ptr()
+        # what the reduce launch is handed (``_reduce``): dr_reduce_update takes
+        # the dr_adam structs themselves; the other rules go through
+        # dr_reduce_update_opt with each wrapped in a dr_optim, and _adam /
+        # _adam_div become views into those (``_wire_packed`` writes through them)
+        lib = _lib.load()
+        if self.optimizer == "adam":
+            self._reduce_entry, self._reduce_name = lib.dr_reduce_update, "dr_reduce_update"
+            self._upd, self._upd_off, self._upd_div = self._adam, self._adam_off, self._adam_div
+        else:
+            self._reduce_entry, self._reduce_name = lib.dr_reduce_update_opt, "dr_reduce_update_opt"
+            self._upd, self._upd_off, self._upd_div = (_lib.OptimC(x, OPT_KINDS[self.optimizer], 1.0 - self.betas[0], 1.0 - self.betas[1], 0) for x in (self._adam, self._adam_off, self._adam_div))
+            self._adam, self._adam_off, self._adam_div = self._upd.adam, self._upd_off.adam, self._upd_div.adam
         self._table_acc = None  # rebuilt on first use (parameters / grads may have moved)
         self._wire_packed()
 
@@ -213,7 +290,7 @@ class FusedTrainStep:
         stored targets.  With N>1 that sum spans all ranks: the pass then runs
         with factor 1, the local sum goes into the all-reduced buffer and Adam
         divides by the reduced one (``device_div``)."""
-        if self.loss == "mse":
+        if self.loss != "ce":  # the regression losses all take MSE's factor
             return 1.0 / (global_batch * self.out_dim if self.out_dim > 1 else global_batch)
         if self.class_weights is None:
             return 1.0 / global_batch
@@ -226,13 +303,17 @@ class FusedTrainStep:
         y = h.store.packed.y[h.gids_host].astype(int)
         self.wsum.fill_(float(self._cw_host[y].sum()))
 
+    def _reduce(self, table, slab, head, n_rows, upd, lpg, scale, lout, stream):
+        """The step's second launch: the partial sums and the update rule of
+        ``self.optimizer`` (``upd``: one of _upd / _upd_off / _upd_div)."""
+        _lib.check(self._reduce_entry(table, slab, head, n_rows, upd, lpg, scale, lout, stream), self._reduce_name)
+
     def _adam_after_allreduce(self):
-        lib = _lib.load()
         stream = _lib.stream_ptr(self.device)
         if self.device_div:
-            _lib.check(lib.dr_reduce_update(self._table, None, None, 0, self._adam_div, None, 1.0, self.loss_out.data_ptr(), stream), "dr_reduce_update")
+            self._reduce(self._table, None, None, 0, self._upd_div, None, 1.0, self.loss_out.data_ptr(), stream)
         else:
-            _lib.check(lib.dr_reduce_update(self._table, None, None, 0, self._adam, None, 1.0, None, stream), "dr_reduce_update")
+            self._reduce(self._table, None, None, 0, self._upd, None, 1.0, None, stream)
 
     def step(self, h: BatchHandle, mask=None, global_batch=None, dropout=True):
         """One training step on the graphs of ``h``; returns (loss [1], out [B,out]) device views.
@@ -268,9 +349,9 @@ class FusedTrainStep:
         table, slab, n_rows = self._reduce_args(h, rows)
         head, lpg, lout = self.head.data_ptr(), self.lpg.data_ptr(), self.loss_out.data_ptr()
         if self.pg is None:
-            _lib.check(lib.dr_reduce_update(table, slab, head, n_rows, self._adam, lpg, scale, lout, stream), "dr_reduce_update")
+            self._reduce(table, slab, head, n_rows, self._upd, lpg, scale, lout, stream)
         else:
-            _lib.check(lib.dr_reduce_update(table, slab, head, n_rows, self._adam_off, lpg, scale, lout, stream), "dr_reduce_update")
+            self._reduce(table, slab, head, n_rows, self._upd_off, lpg, scale, lout, stream)
             if self.device_div:
                 self._local_wsum(h)
             if self.handoffs:
@@ -427,6 +508,12 @@ class FusedTrainStep:
         out = self.spec.layers(self.model, t, (dropout or mask is not None) and self.model.training, mask=mask)
         if self.loss == "mse":
             lpg = (out[:, 0] - t.y) ** 2
+        elif self.loss == "l1" or (self.loss == "smooth_l1" and self.loss_param == 0.0):
+            lpg = torch.nn.functional.l1_loss(out[:, 0], t.y, reduction="none")
+        elif self.loss == "smooth_l1":
+            lpg = torch.nn.functional.smooth_l1_loss(out[:, 0], t.y, reduction="none", beta=self.loss_param)
+        elif self.loss == "huber":
+            lpg = torch.nn.functional.huber_loss(out[:, 0], t.y, reduction="none", delta=self.loss_param)
         else:
             yi = t.y.long()
             lpg = -torch.log_softmax(out, 1).gather(1, yi[:, None])[:, 0]
@@ -451,43 +538,34 @@ class FusedTrainStep:
         self._adam_after_allreduce()
         return self.loss_out, self.out[: h.B]
 
-    # ---- torch.optim.Adam-compatible optimizer state (checkpoints) ----
-    def adam_state_dict(self):
-        """The fused optimizer state as ``torch.optim.Adam(model.parameters()).state_dict()``
-        would hold it (parameter order = the model's ``parameters()`` order)."""
-        opt = torch.optim.Adam(self.params, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
-        t = int(self.counter[0].item())
-        if t > 0:
-            for p, (m, v) in zip(self.params, self.states):
-                opt.state[p] = {"step": torch.tensor(float(t)), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()}
-        return opt.state_dict()
+    # ---- torch-compatible optimizer state (checkpoints) ----
+    def optimizer_state_dict(self):
+        """The fused optimizer state as the matching torch optimizer (Adam /
+        AdamW / Adamax over ``model.parameters()``) would hold it: ``step``,
+        ``exp_avg`` and ``exp_avg_sq`` (Adamax: ``exp_inf``)."""
+        return build_optimizer_state_dict(self.optimizer, self.params, self.states, int(self.counter[0].item()), self.lr, self.betas, self.eps, self.weight_decay)
 
-    def load_adam_state_dict(self, sd):
-        """Inverse of :meth:`adam_state_dict` (also accepts a torch Adam state_dict)."""
-        group = sd["param_groups"][0]
-        if len(group["params"]) != len(self.params) or group.get("amsgrad", False):
-            msg = "optimizer state does not match this model (or uses amsgrad)"
-            raise ValueError(msg)
-        states = sd.get("state", {})
-        steps = set()
-        for slot, (m, v) in zip(group["params"], self.states):
-            st = states.get(slot)
-            if st is None:
-                m.zero_()
-                v.zero_()
-                steps.add(0)
-                continue
-            m.copy_(st["exp_avg"])
-            v.copy_(st["exp_avg_sq"])
-            steps.add(int(float(st["step"])))
-        if len(steps) > 1:
-            msg = f"parameters are at different Adam steps {sorted(steps)}"
-            raise ValueError(msg)
-        t = steps.pop() if steps else 0
+    def load_optimizer_state_dict(self, sd):
+        """Inverse of :meth:`optimizer_state_dict` (also accepts the torch optimizer's state_dict)."""
+        t, self.lr, self.betas, self.eps, self.weight_decay = read_optimizer_state_dict(self.optimizer, sd, self.states)
         self.counter.fill_(t)
         self.step_count = t
-        self.lr, self.betas, self.eps, self.weight_decay = group["lr"], tuple(group["betas"]), group["eps"], group["weight_decay"]
         self._build_structs()
+
+    def adam_state_dict(self):
+        """:meth:`optimizer_state_dict` of a step whose rule is Adam."""
+        self._adam_only()
+        return self.optimizer_state_dict()
+
+    def load_adam_state_dict(self, sd):
+        """:meth:`load_optimizer_state_dict` of a step whose rule is Adam."""
+        self._adam_only()
+        self.load_optimizer_state_dict(sd)
+
+    def _adam_only(self):
+        if self.optimizer != "adam":
+            msg = f"this step's update rule is '{self.optimizer}': use optimizer_state_dict / load_optimizer_state_dict"
+            raise ValueError(msg)
 
     def _state_tensors(self):
         packed = [] if self.wpack is None else [self.wpack[0]]
@@ -577,7 +655,7 @@ class FusedTrainStep:
                 h = handles[i % len(handles)]
                 table, slab, n_rows = self._reduce_args(h, self._acc_rows(h))
                 scale = self.loss_scale(h, global_batch or h.B * self.world)
-                _lib.check(lib.dr_reduce_update(table, slab, self.head.data_ptr(), n_rows, self._adam, self.lpg.data_ptr(), scale, self.loss_out.data_ptr(), stream), "dr_reduce_update")
+                self._reduce(table, slab, self.head.data_ptr(), n_rows, self._upd, self.lpg.data_ptr(), scale, self.loss_out.data_ptr(), stream)
 
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):

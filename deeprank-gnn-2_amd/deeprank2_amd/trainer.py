@@ -6,8 +6,9 @@ early stopping, output exporters and checkpoint keys as the reference
 (``deeprank2/trainer.py:31-1004``).
 
 The hot loop (``_epoch``, trainer.py:666-724) runs, for a model with a fused
-spec (GINet, FoutNet) under the default optimizer (Adam) and loss (MSELoss /
-CrossEntropyLoss, optional class weights), as two HIP launches per
+spec under Adam, AdamW or Adamax and MSELoss / L1Loss / SmoothL1Loss /
+HuberLoss (regression) or CrossEntropyLoss with optional class weights
+(classification) -- :func:`fused_config` decides --, as two HIP launches per
 mini-batch through :class:`~deeprank2_amd.engine.FusedTrainStep` on graphs
 already resident in HBM; losses and outputs stay on the device until the
 epoch ends (one device->host copy per epoch instead of per-step ``.item()``).
@@ -64,6 +65,43 @@ classification_tested = (nn.CrossEntropyLoss, nn.NLLLoss, nn.BCELoss, nn.BCEWith
 
 _OPTIMIZERS = {c.__name__: c for c in (torch.optim.Adam, torch.optim.AdamW, torch.optim.SGD, torch.optim.RMSprop, torch.optim.Adagrad, torch.optim.Adadelta, torch.optim.Adamax, torch.optim.NAdam, torch.optim.RAdam)}
 _LOSSES = {c.__name__: c for c in regression_losses + classification_losses + other_losses}
+
+
+_FUSED_OPTIMIZERS = {torch.optim.Adam: "adam", torch.optim.AdamW: "adamw", torch.optim.Adamax: "adamax"}
+_FUSED_REGRESSION = {nn.MSELoss: ("mse", None), nn.L1Loss: ("l1", None), nn.SmoothL1Loss: ("smooth_l1", "beta"), nn.HuberLoss: ("huber", "delta")}
+
+
+def fused_config(optimizer, lossfunction, task):
+    """What :class:`~deeprank2_amd.engine.FusedTrainStep` is to be built with
+    for this torch optimizer and loss instance, when the kernels compute
+    exactly that configuration: ``(optimizer kind, {"lr", "weight_decay",
+    "betas", "eps"}, loss kind, loss_param, class_weights)``; else ``None``
+    (the generic loop runs).  Pure: reads the two objects only.
+
+    Optimizers: exactly ``torch.optim.Adam`` (with
+    ``decoupled_weight_decay=True``: the AdamW rule), ``AdamW`` or ``Adamax``,
+    one parameter group, a float ``lr``, ``maximize`` and ``amsgrad`` off.
+    Losses, ``reduction="mean"``: MSE / L1 / SmoothL1 / Huber for regression,
+    CrossEntropyLoss (no label smoothing, default ``ignore_index``) for
+    classification."""
+    kind = _FUSED_OPTIMIZERS.get(type(optimizer))
+    if kind is None or len(optimizer.param_groups) != 1:
+        return None
+    g = optimizer.param_groups[0]
+    if g.get("amsgrad") or g.get("maximize") or not isinstance(g["lr"], float):  # (a tensor lr: the generic loop)
+        return None
+    if kind == "adam" and g.get("decoupled_weight_decay"):
+        kind = "adamw"
+    hyper = {"lr": float(g["lr"]), "weight_decay": float(g["weight_decay"]), "betas": tuple(float(b) for b in g["betas"]), "eps": float(g["eps"])}
+    lf = lossfunction
+    if getattr(lf, "reduction", None) != "mean":
+        return None
+    if task == REGRESS and type(lf) in _FUSED_REGRESSION:
+        loss, attr = _FUSED_REGRESSION[type(lf)]
+        return kind, hyper, loss, (float(getattr(lf, attr)) if attr else None), None
+    if task == CLASSIF and type(lf) is nn.CrossEntropyLoss and lf.label_smoothing == 0 and lf.ignore_index == -100:  # noqa: PLR2004
+        return kind, hyper, "ce", None, lf.weight
+    return None
 
 
 class Trainer:
@@ -252,7 +290,8 @@ class Trainer:
                 raise ValueError(msg)
 
     def configure_optimizers(self, optimizer=None, lr: float = 0.001, weight_decay: float = 1e-05):
-        """trainer.py:401-426.  ``None`` -> Adam (the fused path)."""
+        """trainer.py:401-426.  ``None`` -> Adam.  Adam, AdamW and Adamax run on
+        the fused path (:func:`fused_config`); any other optimizer on the generic loop."""
         self.lr = lr
         self.weight_decay = weight_decay
         cls = torch.optim.Adam if optimizer is None else optimizer
@@ -302,24 +341,14 @@ class Trainer:
         """FusedTrainStep when the configuration is exactly what the kernels compute."""
         if self._fused is not None:
             return self._fused or None
-        ok = hasattr(self.model, "fused_spec") and type(self.optimizer) is torch.optim.Adam
-        if ok:
-            g = self.optimizer.param_groups[0]
-            ok = len(self.optimizer.param_groups) == 1 and not g.get("amsgrad") and not g.get("maximize")
-        lf = self.lossfunction
-        loss = None
-        if ok and self.task == REGRESS and type(lf) is nn.MSELoss and lf.reduction == "mean":
-            loss = "mse"
-        elif ok and self.task == CLASSIF and type(lf) is nn.CrossEntropyLoss and lf.reduction == "mean" and lf.label_smoothing == 0 and lf.ignore_index == -100:
-            loss = "ce"
-        if loss is None or self.output_shape > 16 or self.device.type != "cuda":  # noqa: PLR2004
+        cfg = fused_config(self.optimizer, self.lossfunction, self.task) if hasattr(self.model, "fused_spec") else None
+        if cfg is None or self.output_shape > 16 or self.device.type != "cuda":  # noqa: PLR2004
             self._fused = False
             return None
-        g = self.optimizer.param_groups[0]
-        w = lf.weight if loss == "ce" else None
-        step = FusedTrainStep(self.model, lr=g["lr"], weight_decay=g["weight_decay"], betas=tuple(g["betas"]), eps=g["eps"], loss=loss, class_weights=w, process_group=self.process_group)
+        kind, hyper, loss, loss_param, w = cfg
+        step = FusedTrainStep(self.model, **hyper, loss=loss, loss_param=loss_param, class_weights=w, optimizer=kind, process_group=self.process_group)
         if self.optimizer.state:
-            step.load_adam_state_dict(self.optimizer.state_dict())
+            step.load_optimizer_state_dict(self.optimizer.state_dict())
         self._fused = step
         return step
 
@@ -470,7 +499,7 @@ class Trainer:
         self.optimizer.load_state_dict(self.opt_loaded_state_dict)
         self.model.load_state_dict(self.model_load_state_dict)
         if self._fused:
-            self._fused.load_adam_state_dict(self.opt_loaded_state_dict)
+            self._fused.load_optimizer_state_dict(self.opt_loaded_state_dict)
 
     def _epoch(self, epoch_number: int, pass_name: str):
         """trainer.py:666-724: one pass over the training loader."""
@@ -749,7 +778,7 @@ class Trainer:
     # ------------------------------------------------------------ checkpoints
     def _optimizer_state(self):
         if self._fused:
-            return self._fused.adam_state_dict()
+            return self._fused.optimizer_state_dict()
         return self.optimizer.state_dict()
 
     def _save_model(self):

@@ -25,6 +25,9 @@
  *                           optimizer.step() of Trainer._epoch
  *                           (trainer.py:689-690; torch.optim.Adam configured at
  *                           trainer.py:419)
+ *   dr_reduce_update_opt    the same with torch.optim.AdamW / Adamax (the reference's
+ *                           documented configure_optimizers(torch.optim.Adamax, ...),
+ *                           README.md:386)
  *   dr_spmm_csr             torch_scatter.scatter_sum(h, row, out=zeros) over
  *                           gathered rows (ginet.py:45,55-58; vanilla_gnn.py:35)
  *   dr_spmm_csr_w           the edge-weighted scatter_mean of
@@ -148,6 +151,12 @@ typedef struct dr_ginet_weights {
 #define DR_LOSS_NONE 0      /* dout is an input (autograd)                       */
 #define DR_LOSS_MSE 1       /* nn.MSELoss(mean) on pred.reshape(-1)               */
 #define DR_LOSS_CE 2        /* nn.CrossEntropyLoss(mean, optional class weights)  */
+/* The other regression losses the reference accepts (deeprank2/domain/losstypes.py:3-8),
+ * on d = out[b,0] - y_b like DR_LOSS_MSE: the unscaled per-graph term goes to
+ * loss_per_graph, dout[0] = (d term / d d) * loss_scale, the other dout[q] = 0. */
+#define DR_LOSS_L1 3        /* nn.L1Loss(mean): |d|; gradient sign(d), 0 at d == 0 and at NaN */
+#define DR_LOSS_SMOOTH_L1 4 /* nn.SmoothL1Loss(mean, beta = loss_param >= 0; beta == 0: L1) */
+#define DR_LOSS_HUBER 5     /* nn.HuberLoss(mean, delta = loss_param > 0)            */
 
 #define DR_SLAB_STRIDE(F) (32 * (F) + 1024)
 #define DR_HEAD_STRIDE(out) (320 + (((out) + 3) & ~3))
@@ -168,7 +177,7 @@ typedef struct dr_pass {
   float drop_p;         /* p (DR_DROPOUT_HASH)                                 */
   uint64_t drop_seed;   /* DR_DROPOUT_HASH: keep[b,r] = u(seed, offset, 128b+r) >= p */
   uint64_t drop_offset;
-  float loss_scale;     /* 1/B (MSE) or 1/sum(w_y) (CE)                        */
+  float loss_scale;     /* 1/B (MSE, L1, SmoothL1, Huber) or 1/sum(w_y) (CE)   */
   int32_t compute_dtype;/* DR_DTYPE_F32, or DR_DTYPE_BF16: the conv1 node GEMM takes bf16
                            operands (x from store->x_bf16, Z = A x rounded to bf16, W1
                            rounded to bf16) on the bf16 MFMA with fp32 accumulate; all
@@ -197,7 +206,9 @@ typedef struct dr_pass {
                            ticket); otherwise one give-up stays set and every later step is
                            withheld with a NaN loss.                                      */
   int32_t spin_limit;   /* polls before a hand-off wait gives up (<= 0: 1 << 22)        */
-  int32_t pad0;
+  float loss_param;     /* DR_LOSS_SMOOTH_L1: beta; DR_LOSS_HUBER: delta; ignored otherwise.
+                           Every graph-pass entry returns DR_E_ARG for an unknown loss_kind,
+                           beta < 0, delta <= 0 or a non-finite value of a parameter it reads */
   const int32_t* slot;  /* optional device [B] (GINet / FoutNet / SGAT passes): launch position b
                            writes row slot[b] of out, loss_per_graph, slab, head and reads row
                            slot[b] of dout / mask, and draws dropout unit slot[b] -- a batch run
@@ -637,6 +648,33 @@ typedef struct dr_param_table {
 int dr_reduce_update(const dr_param_table* t, const float* slab, const float* head, int32_t n_batch,
                      const dr_adam* adam, const float* loss_per_graph, float loss_scale, float* loss_out,
                      void* stream);
+
+/* The same launch with the update rule chosen by kind (reduce_optim.hip; one
+ * kernel instantiation per kind, picked on the host).  Everything dr_adam
+ * carries holds for every kind: step_counter, fault, grad_div, mirror /
+ * mirror_idx, fault_clear / ticket, enabled.  Rules as torch 2.10's
+ * _single_tensor_* functions with maximize=False:
+ *   DR_OPT_ADAM    torch.optim.Adam: the arithmetic of dr_reduce_update
+ *   DR_OPT_ADAMW   torch.optim.AdamW (= Adam(decoupled_weight_decay=True)):
+ *                  p *= 1 - lr*wd, the moments from the raw gradient, then Adam's step
+ *   DR_OPT_ADAMAX  torch.optim.Adamax: g += wd*p; m = lerp(m, g, 1-beta1);
+ *                  u = max(u*beta2, |g| + eps) (NaN propagates);
+ *                  p -= lr / (1 - beta1^t) * m / u.  The table's exp_avg_sq[i]
+ *                  carries exp_inf; bias_c2_sqrt is unused.
+ * An unknown kind returns DR_E_ARG.                                          */
+#define DR_OPT_ADAM 0
+#define DR_OPT_ADAMW 1
+#define DR_OPT_ADAMAX 2
+typedef struct dr_optim {
+  dr_adam adam;
+  int32_t kind; /* DR_OPT_* */
+  float om_beta1; /* 1 - beta1 and 1 - beta2 rounded from double, as torch forms the     */
+  float om_beta2; /* lerp / addcmul weights (1 - 0.999f is 1.3e-5 off 0.001f); 0: 1.f - beta */
+  int32_t pad0;
+} dr_optim;
+int dr_reduce_update_opt(const dr_param_table* t, const float* slab, const float* head, int32_t n_batch,
+                         const dr_optim* opt, const float* loss_per_graph, float loss_scale, float* loss_out,
+                         void* stream);
 
 /* ---- generic layer kernels (arbitrary edge lists; GINetConvLayer API) ---- */
 
