@@ -18,6 +18,9 @@ Contents
 ``gnn_ref``    op-for-op torch-CPU restatement of ``deeprank2/neuralnets/gnn``
                (GINet, FoutNet, VanillaNetwork) and
                ``deeprank2/utils/community_pooling.py``.
+``bf16_ref``   ``gnn_ref.GINet`` with the three rounding points of the bf16
+               compute mode (x, Z = A x, W1 to bf16; swappable quantisers),
+               written from the kernel's documented arithmetic.
 ``data_ref``   restatement of ``GraphDataset.load_one_graph`` + PyG collate over
                the ``.npz`` dump of the HDF5 fixtures.
 ``mcl_ref``    numpy restatement of networkx's adjacency + markov_clustering

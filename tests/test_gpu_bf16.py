@@ -12,6 +12,7 @@ master weights and fp32 Adam.  Checked against the fp32 oracle
 * gradients: ||g - ref|| <= 3e-2 * ||ref|| per parameter tensor (normwise:
   individual entries near zero carry the absolute rounding noise);
 * the loss to 2e-2 relative.
+(``test_gpu_bf16_parity.py`` checks the same kernels at the fp32 tolerance against an oracle that rounds where they do.)
 """
 
 from __future__ import annotations
