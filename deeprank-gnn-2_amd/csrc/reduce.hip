@@ -1,14 +1,17 @@
-// Gradient reduction over the batch + Adam for one block of parameter
-// elements (the stand-alone reduce kernel, reduce_adam.hip; the r03-r05
-// one-launch GINet steps that also ran it are gone).  r06 measured and did
-// not keep blocks that stage their partials in LDS first (outer products and
-// row sums): 3.9 vs 3.5 us per launch, the load -> LDS -> barrier -> sum
-// chain is longer than the direct loads (profiles/r06/not_kept/).
+// Gradient reduction over the batch + the optimizer update, the second launch
+// of every fused model's training step (dr_reduce_update: torch.optim.Adam;
+// dr_reduce_update_opt: Adam, AdamW or Adamax by dr_optim.kind).
 //
 // Replaces loss_.backward()'s accumulation over the batch and
-// optimizer.step() of Trainer._epoch (deeprank2/trainer.py:689-690; Adam
-// configured at trainer.py:419).
-#pragma once
+// optimizer.step() of Trainer._epoch (deeprank2/trainer.py:689-690) for the
+// optimizers a user hands to Trainer.configure_optimizers (trainer.py:401-428;
+// Adam by default, the reference's README configures torch.optim.Adamax).
+// Each parameter element's gradient is a sum over the per-graph partials the
+// graph pass wrote (slab rows, or outer products of per-graph head vectors),
+// taken in a fixed order: deterministic, no float atomics.  HBM-bound on the
+// partials (~0.6 MB per GINet step at B=64).  The update rule is the kernel's
+// compile-time OPT, one instantiation per kind chosen on the host, so no kind
+// pays a branch for another.
 
 #include <hip/hip_runtime.h>
 
@@ -18,14 +21,37 @@
 #include "../../include/deeprank2_amd.h"
 #include "dr_common.h"
 
-namespace drr {
-
 #ifndef DR_RP
 #define DR_RP 64
 #endif
 #ifndef DR_RC
 #define DR_RC 8
 #endif
+#define DR_REDUCE_MAX_BLOCKS 512  // 32 K parameter elements (GINet at F=64: ~11.5 K)
+
+// Diagnostic timeline (stamps build only, dr_debug_reduce_stamps): thread 0
+// of block j writes s_memrealtime (100 MHz chip clock) at point i to
+// g_reduce_stamps[j * 8 + i]: 0 entry, 5 kernel-argument record in, 1 its
+// partials summed, 2 past the barrier, 3 stores issued, 4 stores done.
+#ifdef DR_STAMPS
+namespace drr {
+__device__ int64_t g_reduce_stamps[4096 * 8];
+}
+static_assert(DR_REDUCE_MAX_BLOCKS <= 4096, "one stamp row per block of the largest grid");
+#define RDSTAMP(i)                                                                                      \
+  do {                                                                                                  \
+    __builtin_amdgcn_sched_barrier(0);                                                                  \
+    if (threadIdx.x == 0) drr::g_reduce_stamps[(int64_t)blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); \
+    __builtin_amdgcn_sched_barrier(0);                                                                  \
+  } while (0)
+#else
+#define RDSTAMP(i) \
+  do {             \
+  } while (0)
+#endif
+
+namespace {
+
 constexpr int RP = DR_RP;  // parameter elements per block
 constexpr int RC = DR_RC;  // batch chunks per block
 constexpr int RU = 8;   // batch rows per chunk issued together (predicated)
@@ -53,83 +79,54 @@ struct alignas(64) ReduceHdr {
   const uint32_t* fault;  // dr_adam.fault: nonzero -> NaN loss / gradients, no update
   int32_t B, slab_stride, head_stride, adam_enabled;
   float loss_scale, pad0;
+  // pad0, n_params, blk0: read by no kernel, left zero.  They stay because
+  // taking them out moves every later field and the block map, and hipcc then
+  // schedules the kernels differently (not only other scalar-load offsets).
   float lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2_sqrt;
   float wd_mul;  // 1 - lr * weight_decay (AdamW's decoupled decay factor)
   float log2_beta1, log2_beta2;  // beta^t = exp2(t log2 beta): one v_exp_f32, not powf
-  int32_t n_params, n_blocks;
-  int16_t blk0[DR_MAX_PARAMS + 1];  // first block of each parameter (prefix sums of ceil(numel / RP)), blk0[n_params] = n_blocks
+  int32_t n_params, n_blocks;  // n_blocks: the grid, sum of ceil(numel / RP) (the fault_clear ticket counts to it)
+  int16_t blk0[DR_MAX_PARAMS + 1];
   int32_t slab_rows;  // slab rows per graph (>= 1): a slab-kind gradient sums B * slab_rows rows
   float* mirror;            // dr_adam.mirror / mirror_idx: packed copies of updated elements
   const int4* mirror_idx;
-  uint32_t* fault_clear;    // dr_adam.fault_clear / ticket (stand-alone reduce kernel only)
+  uint32_t* fault_clear;    // dr_adam.fault_clear / ticket
   uint32_t* ticket;
-  // dr_optim.om_beta1 / om_beta2 (the rules of reduce_optim.hip; the Adam
-  // kernel forms 1.f - beta itself, as it always has)
+  // dr_optim.om_beta1 / om_beta2 (AdamW, Adamax; the Adam instantiation forms
+  // 1.f - beta itself)
   float om_beta1, om_beta2;
 };
 
-typedef __attribute__((address_space(1))) unsigned int gu32r;
-
-// Diagnostic timeline (stamps build only, dr_debug_reduce_stamps): thread 0
-// of block j writes s_memrealtime (100 MHz chip clock) at point i to
-// g_reduce_stamps[j * 8 + i]: 0 entry, 5 kernel-argument record in, 1 its
-// partials summed, 2 past the barrier, 3 stores issued, 4 stores done.
-#ifdef DR_STAMPS
-__device__ int64_t g_reduce_stamps[4096 * 8];
-#define RDSTAMP(i)                                                                                      \
-  do {                                                                                                  \
-    __builtin_amdgcn_sched_barrier(0);                                                                  \
-    if (threadIdx.x == 0) drr::g_reduce_stamps[(int64_t)blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); \
-    __builtin_amdgcn_sched_barrier(0);                                                                  \
-  } while (0)
-#else
-#define RDSTAMP(i) \
-  do {             \
-  } while (0)
-#endif
-
-// LD: how the partials are read.  0: plain loads (written by an earlier
-// launch).  1: agent-scope relaxed atomic loads (sc1: past this CU's L1) and
-// 2: system-scope ones, for partials published inside the same launch by
-// write-through stores of other workgroups (MI355X_MICROARCH.md
-// §inter-workgroup visibility).
-template <int LD>
-__device__ __forceinline__ float ld_part(const float* p) {
-  if (LD == 1) return __uint_as_float(__hip_atomic_load((const gu32r*)(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-  if (LD == 2) return __uint_as_float(__hip_atomic_load((const gu32r*)(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-  return *p;
-}
+struct alignas(64) ReduceArgs {
+  ReduceHdr h;
+  ParamRec rec[DR_MAX_PARAMS];
+  // 1-D grid: block -> (parameter, first element); blocks never straddle two parameters
+  uint8_t blk_param[DR_REDUCE_MAX_BLOCKS];
+  uint16_t blk_elem[DR_REDUCE_MAX_BLOCKS];  // first element / RP
+};
 
 // One block = RP consecutive elements (from elem_block * RP) of parameter r,
 // RC batch chunks per element; t = thread index within the block's RT
 // threads, part = the block's [RC][RP] LDS scratch.  first: the block that
-// also sums the loss and advances the step counter.  tstep: the Adam step
-// (counter[1] + 1) when h.step_counter is set.  Every load of the block is
+// also sums the loss and advances the step counter.  tstep: the optimizer
+// step (counter[1] + 1) when h.step_counter is set.  The partials were
+// written by an earlier launch (plain loads).  Every load of the block is
 // issued in one straight-line group (clamped indices, zero weights past the
-// batch), so one wait covers the partials and the Adam state.  The caller
-// synchronises the workgroup between two calls that share `part`.
-// WTP: the updated parameters are stored write-through (agent scope), for a
-// launch whose other workgroups read them after a grid-wide hand-off (the
-// reduce-at-start GINet step, ginet_fused.hip).
-// row_off: the partials of graph b sit at row row_off + b (slab: (row_off + b)
-// * slab_rows): the half of the pipelined step's double buffer.
-// OPT: the update rule (DR_OPT_*), fixed at compile time: the Adam
-// instantiation carries no branch for the others (reduce_optim.hip has them).
-template <int LD, bool LEAN = false, bool WTP = false, int OPT = DR_OPT_ADAM>
+// batch), so one wait covers the partials and the optimizer state.
+// OPT: the update rule (DR_OPT_*).
+template <int OPT>
 __device__ __forceinline__ void reduce_block(const ReduceHdr& h, const ParamRec& r, int elem_block, bool first, int t,
-                                             float (*part)[RP], int64_t tstep, int64_t row_off = 0) {
-  // LEAN: partials always given, Adam always on (the one-launch step): the
-  // gradients-supplied path is compiled out (less code to fetch cold)
+                                             float (*part)[RP], int64_t tstep) {
   const int lp = t % RP, ch = t / RP;
   const int e = elem_block * RP + lp;
   const bool live = e < r.numel;
   // a graph pass whose in-launch hand-off gave up (dr_pass.fault): its
   // partials are wrong, so the step reports NaN and changes no state
-  const uint32_t fv = (!LEAN && h.fault) ? *h.fault : 0u;
+  const uint32_t fv = h.fault ? *h.fault : 0u;
   const bool bad = fv != 0u;
   if (first && t < 64 && h.lpg && h.loss_out) {
     float acc = 0.f;  // lane-strided partial sums, then a fixed-order wave reduction
-    for (int b = t; b < h.B; b += 64) acc += ld_part<LD>(h.lpg + row_off + b);
+    for (int b = t; b < h.B; b += 64) acc += h.lpg[b];
     acc = dr_wave_sum(acc);
     if (t == 0) h.loss_out[0] = bad ? __builtin_nanf("") : acc * h.loss_scale;
   } else if (bad && first && t == 0 && h.loss_out) {
@@ -139,7 +136,7 @@ __device__ __forceinline__ void reduce_block(const ReduceHdr& h, const ParamRec&
   const bool slab_kind = r.kind == DR_GRAD_SLAB, outer = r.kind == DR_GRAD_OUTER;
   const bool has_src = h.slab && (slab_kind || outer || r.kind == DR_GRAD_HEAD);
   const int64_t st = slab_kind ? h.slab_stride : h.head_stride;
-  const float* base = (slab_kind ? h.slab : h.head) + row_off * (slab_kind ? h.slab_rows : 1) * st;
+  const float* base = slab_kind ? h.slab : h.head;
   const int col1 = outer ? r.off1 + ec / r.cols : r.off1 + ec;
   const int col2 = outer ? r.off2 + ec % r.cols : 0;
   const int nb = slab_kind ? h.B * h.slab_rows : h.B;  // rows of this gradient's partials
@@ -149,21 +146,21 @@ __device__ __forceinline__ void reduce_block(const ReduceHdr& h, const ParamRec&
 #pragma unroll
     for (int k = 0; k < RU; ++k) {
       const int64_t row = min(b0 + k, b1 - 1);
-      u[k] = ld_part<LD>(base + row * st + col1);
-      w[k] = outer ? ld_part<LD>(base + row * st + col2) : 1.f;
+      u[k] = base[row * st + col1];
+      w[k] = outer ? base[row * st + col2] : 1.f;
     }
   }
-  const bool upd = live && ch == 0 && (LEAN || h.adam_enabled) && !bad;
+  const bool upd = live && ch == 0 && h.adam_enabled && !bad;
   float p0 = 0.f, m0 = 0.f, v0 = 0.f, gin = 0.f;
   int4 mi = make_int4(-1, -1, -1, -1);  // dr_adam.mirror slots of this element, loaded with the state
-  if (ch == 0 && (LEAN || h.adam_enabled) && r.numel > 0) {  // numel 0: an empty record (no pointers)
+  if (ch == 0 && h.adam_enabled && r.numel > 0) {  // numel 0: an empty record (no pointers)
     p0 = r.param[ec];
     m0 = r.m[ec];
     v0 = r.v[ec];
-    if (!LEAN && h.mirror) mi = h.mirror_idx[r.mbase + ec];
+    if (h.mirror) mi = h.mirror_idx[r.mbase + ec];
   }
   float div = 1.f;
-  if (!LEAN && ch == 0 && !h.slab && r.grad) {
+  if (ch == 0 && !h.slab && r.grad) {
     gin = r.grad[ec];
     if (h.grad_div) div = *h.grad_div;
   }
@@ -180,8 +177,8 @@ __device__ __forceinline__ void reduce_block(const ReduceHdr& h, const ParamRec&
 #pragma unroll
         for (int k = 0; k < RU2; ++k) {
           const int64_t row = min(bb + k, b1 - 1);
-          u2[k] = ld_part<LD>(base + row * st + col1);
-          w2[k] = outer ? ld_part<LD>(base + row * st + col2) : 1.f;
+          u2[k] = base[row * st + col1];
+          w2[k] = outer ? base[row * st + col2] : 1.f;
         }
 #pragma unroll
         for (int k = 0; k < RU2; ++k)
@@ -197,20 +194,20 @@ __device__ __forceinline__ void reduce_block(const ReduceHdr& h, const ParamRec&
   // dr_adam.fault_clear: lane 0 of each block takes a ticket once its read of
   // the flag has returned; the last block's lane 0 clears the flag (every
   // block has read it by then) for the next graph pass
-  const bool tick = !LEAN && h.fault_clear && lp == 0;
+  const bool tick = h.fault_clear && lp == 0;
   uint32_t tk = 0u;
   if (tick) {
     asm volatile("" ::"v"(fv) : "memory");
     tk = __hip_atomic_fetch_add(h.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   float gsum;
-  if (LEAN || h.slab) {
+  if (h.slab) {
     gsum = 0.f;
 #pragma unroll
     for (int k = 0; k < RC; ++k) gsum += part[k][lp];
     if (bad) gsum = __builtin_nanf("");
     if (r.grad) r.grad[e] = gsum;
-  } else {  // gradients supplied (e.g. after an RCCL all-reduce): Adam only
+  } else {  // gradients supplied (e.g. after an RCCL all-reduce): the update only
     gsum = gin;
     if (h.grad_div) {
       gsum = gin / div;
@@ -224,10 +221,10 @@ __device__ __forceinline__ void reduce_block(const ReduceHdr& h, const ParamRec&
     if (h.step_counter) {  // step and bias corrections from the device counter
       bc1 = 1.f - exp2f((float)tstep * h.log2_beta1);
       bc2s = sqrtf(1.f - exp2f((float)tstep * h.log2_beta2));
-      if (!LEAN && first && lp == 0) h.step_counter[0] = tstep;  // LEAN: the caller advances it
+      if (first && lp == 0) h.step_counter[0] = tstep;
     }
-    // every product-sum spelled out (fmaf / __fmul_rn / __fadd_rn): contraction
-    // is then the same in every kernel that inlines this block
+    // every product-sum spelled out (fmaf / __fmul_rn / __fadd_rn): no
+    // contraction is left to the compiler
     float gr = gsum, pb = p0;  // the gradient and the parameter the rule starts from
     if constexpr (OPT == DR_OPT_ADAMW) {
       // torch.optim.AdamW (_single_tensor_adam, decoupled_weight_decay):
@@ -261,9 +258,8 @@ __device__ __forceinline__ void reduce_block(const ReduceHdr& h, const ParamRec&
       const float denom = __fadd_rn(__fdiv_rn(sqrtf(vv), bc2s), h.eps);
       pn = fmaf(-(h.lr / bc1), __fdiv_rn(mv, denom), pb);
     }
-    if (WTP) __hip_atomic_store((__attribute__((address_space(1))) unsigned int*)(r.param + e), __float_as_uint(pn), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else r.param[e] = pn;
-    if (!LEAN && h.mirror) {
+    r.param[e] = pn;
+    if (h.mirror) {
       if (mi.x >= 0) h.mirror[mi.x] = pn;
       if (mi.y >= 0) h.mirror[mi.y] = pn;
       if (mi.z >= 0) h.mirror[mi.z] = pn;
@@ -281,11 +277,32 @@ __device__ __forceinline__ void reduce_block(const ReduceHdr& h, const ParamRec&
   RDSTAMP(4);
 }
 
-// Host: header + records from the C-ABI table and Adam settings; returns the
-// number of RP-element blocks, or a negative DR_E_* code.
-inline int build_reduce(const dr_param_table* t, const float* slab, const float* head, int32_t n_batch,
-                        const dr_adam* adam, const float* loss_per_graph, float loss_scale, float* loss_out,
-                        ReduceHdr& h, ParamRec* rec) {
+// 1-D grid over sum_p ceil(numel_p / RP) blocks: block j reduces RP
+// consecutive elements of parameter blk_param[j] and applies rule OPT to
+// them.  Its record and the header are scalar loads from the kernel arguments.
+template <int OPT>
+__global__ void __launch_bounds__(RT) reduce_kernel(ReduceArgs a) {
+  __shared__ float part[RC][RP];
+  RDSTAMP(0);
+  const int pi = a.blk_param[blockIdx.x];
+  const ParamRec r = a.rec[pi];
+  // Pull every kernel-argument line this block uses in one scalar round trip
+  // (hipcc would otherwise issue them lazily, one wait each).
+  {
+    const float *slab = a.h.slab, *head = a.h.head;
+    const int32_t B = a.h.B, ss = a.h.slab_stride, hs = a.h.head_stride, en = a.h.adam_enabled;
+    asm volatile("" ::"s"(slab), "s"(head), "s"(B), "s"(ss), "s"(hs), "s"(en), "s"(r.param), "s"(r.grad), "s"(r.m),
+                 "s"(r.v), "s"(r.numel), "s"(r.kind), "s"(r.off1), "s"(r.off2), "s"(r.cols));
+  }
+  RDSTAMP(5);  // (stamps build: the block's kernel-argument record is in)
+  const int64_t tstep = (a.h.step_counter && a.h.adam_enabled) ? a.h.step_counter[1] + 1 : 0;
+  reduce_block<OPT>(a.h, r, a.blk_elem[blockIdx.x], blockIdx.x == 0, threadIdx.x, part, tstep);
+}
+
+// Host: header + records from the C-ABI table and optimizer settings; returns
+// the number of RP-element blocks, or a negative DR_E_* code.
+int build_reduce(const dr_param_table* t, const float* slab, const float* head, int32_t n_batch, const dr_adam* adam,
+                 const float* loss_per_graph, float loss_scale, float* loss_out, ReduceHdr& h, ParamRec* rec) {
   if (!t || !adam || n_batch < 0) return DR_E_ARG;
   if ((slab == nullptr) != (head == nullptr)) return DR_E_ARG;
   if (t->n_params < 1 || t->n_params > DR_MAX_PARAMS) return DR_E_ARG;
@@ -339,16 +356,62 @@ inline int build_reduce(const dr_param_table* t, const float* slab, const float*
     pr.cols = r.cols;
     pr.mbase = mbase;
     mbase += t->numel[i];
-    h.blk0[i] = (int16_t)blocks;
     blocks += (t->numel[i] + RP - 1) / RP;
   }
   if (blocks > 32767) return DR_E_UNSUPPORTED;
-  for (int i = t->n_params; i <= DR_MAX_PARAMS; ++i) h.blk0[i] = (int16_t)blocks;
-  h.n_params = t->n_params;
   h.n_blocks = blocks;
   if (t->slab_rows < 0 || t->slab_rows > 64) return DR_E_ARG;
   h.slab_rows = t->slab_rows > 0 ? t->slab_rows : 1;
   return blocks;
 }
 
-}  // namespace drr
+// Everything up to the launch, for a rule already validated by the caller.
+// om_beta*: 0 = 1.f - beta (the Adam kernel does not read them).
+int reduce_launch(int kind, const dr_param_table* t, const float* slab, const float* head, int32_t n_batch,
+                  const dr_adam* adam, float om_beta1, float om_beta2, const float* loss_per_graph, float loss_scale,
+                  float* loss_out, void* stream) {
+  ReduceArgs a;
+  std::memset(&a, 0, sizeof(a));
+  const int blocks = build_reduce(t, slab, head, n_batch, adam, loss_per_graph, loss_scale, loss_out, a.h, a.rec);
+  if (blocks < 0) return blocks;
+  if (blocks > DR_REDUCE_MAX_BLOCKS) return DR_E_UNSUPPORTED;
+  a.h.om_beta1 = om_beta1 != 0.f ? om_beta1 : 1.f - adam->beta1;
+  a.h.om_beta2 = om_beta2 != 0.f ? om_beta2 : 1.f - adam->beta2;
+  int j = 0;
+  for (int i = 0; i < t->n_params; ++i)
+    for (int x = 0; x * RP < t->numel[i]; ++x, ++j) {
+      a.blk_param[j] = (uint8_t)i;
+      a.blk_elem[j] = (uint16_t)x;
+    }
+  if (blocks == 0) return DR_OK;
+  auto kernel = kind == DR_OPT_ADAMW    ? reduce_kernel<DR_OPT_ADAMW>
+                : kind == DR_OPT_ADAMAX ? reduce_kernel<DR_OPT_ADAMAX>
+                                        : reduce_kernel<DR_OPT_ADAM>;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(RT), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int dr_reduce_update(const dr_param_table* t, const float* slab, const float* head, int32_t n_batch,
+                                const dr_adam* adam, const float* loss_per_graph, float loss_scale, float* loss_out,
+                                void* stream) {
+  return reduce_launch(DR_OPT_ADAM, t, slab, head, n_batch, adam, 0.f, 0.f, loss_per_graph, loss_scale, loss_out, stream);
+}
+
+extern "C" int dr_reduce_update_opt(const dr_param_table* t, const float* slab, const float* head, int32_t n_batch,
+                                    const dr_optim* opt, const float* loss_per_graph, float loss_scale,
+                                    float* loss_out, void* stream) {
+  if (!opt) return DR_E_ARG;
+  if (opt->kind != DR_OPT_ADAM && opt->kind != DR_OPT_ADAMW && opt->kind != DR_OPT_ADAMAX) return DR_E_ARG;
+  return reduce_launch(opt->kind, t, slab, head, n_batch, &opt->adam, opt->om_beta1, opt->om_beta2, loss_per_graph,
+                       loss_scale, loss_out, stream);
+}
+
+#ifdef DR_STAMPS
+// stamps build only: the reduce kernel's timeline stamps (of whichever kind ran last)
+extern "C" int dr_debug_reduce_stamps(int64_t* host, int32_t n) {
+  if (!host || n < 0 || n > 4096 * 8) return DR_E_ARG;
+  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(drr::g_reduce_stamps), (size_t)n * sizeof(int64_t), 0, hipMemcpyDeviceToHost);
+}
+#endif

@@ -6,11 +6,10 @@ for any model with a ``fused_spec`` (GINet, FoutNet).
    FORWARD|BACKWARD, loss in-kernel): one workgroup per graph computes the
    prediction, the loss term and the whole backward of its graph, writing
    per-graph partials;
-2. ``dr_reduce_update``: sums the partials into every gradient and
+2. ``dr_reduce_update_opt``: sums the partials into every gradient and
    applies ``torch.optim.Adam`` (lr, betas, eps, L2 ``weight_decay`` as
-   ``Trainer.configure_optimizers`` sets them, trainer.py:401-428); with
-   ``optimizer="adamw"`` / ``"adamax"`` the same launch through
-   ``dr_reduce_update_opt`` applies ``torch.optim.AdamW`` / ``Adamax``.
+   ``Trainer.configure_optimizers`` sets them, trainer.py:401-428), or with
+   ``optimizer="adamw"`` / ``"adamax"`` ``torch.optim.AdamW`` / ``Adamax``.
 
 The in-kernel loss is ``loss``: "mse" / "ce", or "l1" / "smooth_l1" / "huber"
 (``loss_param``: SmoothL1Loss's beta, HuberLoss's delta), the regression
@@ -30,12 +29,14 @@ reduced gradients.  That is the only collective (``distributed.py`` shards).
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import torch
 
 from deeprank2_amd import _lib, layered
-from deeprank2_amd.fused import BatchHandle, launch, param_table, slab_rows_for
+from deeprank2_amd.fused import BatchHandle, _device_cus, launch, lds_for, param_table, slab_rows_for
+from deeprank2_amd.neuralnets.gnn.ginet import acc_recipe
 
 
 # FusedTrainStep's ``loss`` / ``optimizer`` names -> DR_LOSS_* / DR_OPT_*
@@ -230,24 +231,17 @@ class FusedTrainStep:
         # world of one: this step's own flag; N>1: the all-reduced one (the
         # partial reduce before the all-reduce NaNs the rank's gradients)
         a.fault = (self.fault if self.pg is None else self.fault_red).data_ptr()
-        self._adam = a
-        self._adam_off = _lib.AdamC.from_buffer_copy(a)
+        # what the reduce launch is handed (``_reduce``): the update, the
+        # gradients-only launch before an all-reduce, and the update that
+        # divides by the all-reduced weight sum.  1 - beta is formed in double
+        # as torch forms it (Adam's kernel takes its own fp32 complement: 0).
+        om = (0.0, 0.0) if self.optimizer == "adam" else (1.0 - self.betas[0], 1.0 - self.betas[1])
+        self._upd, self._upd_off, self._upd_div = (_lib.OptimC(a, OPT_KINDS[self.optimizer], *om, 0) for _ in range(3))
+        # the dr_adam inside each (``_wire_packed`` writes through these views)
+        self._adam, self._adam_off, self._adam_div = self._upd.adam, self._upd_off.adam, self._upd_div.adam
         self._adam_off.enabled = 0
         self._adam_off.fault = self.fault.data_ptr()
-        self._adam_div = _lib.AdamC.from_buffer_copy(a)
         self._adam_div.grad_div = self.wsum.data_ptr()
-        # what the reduce launch is handed (``_reduce``): dr_reduce_update takes
-        # the dr_adam structs themselves; the other rules go through
-        # dr_reduce_update_opt with each wrapped in a dr_optim, and _adam /
-        # _adam_div become views into those (``_wire_packed`` writes through them)
-        lib = _lib.load()
-        if self.optimizer == "adam":
-            self._reduce_entry, self._reduce_name = lib.dr_reduce_update, "dr_reduce_update"
-            self._upd, self._upd_off, self._upd_div = self._adam, self._adam_off, self._adam_div
-        else:
-            self._reduce_entry, self._reduce_name = lib.dr_reduce_update_opt, "dr_reduce_update_opt"
-            self._upd, self._upd_off, self._upd_div = (_lib.OptimC(x, OPT_KINDS[self.optimizer], 1.0 - self.betas[0], 1.0 - self.betas[1], 0) for x in (self._adam, self._adam_off, self._adam_div))
-            self._adam, self._adam_off, self._adam_div = self._upd.adam, self._upd_off.adam, self._upd_div.adam
         self._table_acc = None  # rebuilt on first use (parameters / grads may have moved)
         self._wire_packed()
 
@@ -306,7 +300,7 @@ class FusedTrainStep:
     def _reduce(self, table, slab, head, n_rows, upd, lpg, scale, lout, stream):
         """The step's second launch: the partial sums and the update rule of
         ``self.optimizer`` (``upd``: one of _upd / _upd_off / _upd_div)."""
-        _lib.check(self._reduce_entry(table, slab, head, n_rows, upd, lpg, scale, lout, stream), self._reduce_name)
+        _lib.check(_lib.load().dr_reduce_update_opt(table, slab, head, n_rows, upd, lpg, scale, lout, stream), "dr_reduce_update_opt")
 
     def _adam_after_allreduce(self):
         stream = _lib.stream_ptr(self.device)
@@ -365,8 +359,6 @@ class FusedTrainStep:
     def _acc_rows(self, h: BatchHandle) -> int:
         """Workgroups (= partial rows) of the accumulating pass for this
         batch, or 0 when the batch takes the per-graph partials."""
-        from deeprank2_amd.fused import _device_cus, lds_for  # noqa: PLC0415
-
         if self.acc is False or self.spec.entry != "dr_ginet_graph_pass" or self.compute_dtype != "f32":
             return 0
         if h.nonfinite or h.force_large or self.spec.layers is not None and layered.needs_layers(self.spec, h, self.out_dim):
@@ -385,17 +377,8 @@ class FusedTrainStep:
         if self._acc_slab is None or self._acc_slab.numel() < r * rs:
             self._acc_slab = torch.empty(r * rs, dtype=torch.float32, device=self.device)
         if self._table_acc is None:
-            from deeprank2_amd.fused import param_table  # noqa: PLC0415
-
             self._table_acc = param_table(self.spec, self.params, self.grads, self.states, f, self.out_dim)
-            slab, z = _lib.DR_GRAD_SLAB, (_lib.DR_GRAD_ZERO, 0, 0, 0)
-            c0 = 32 * f + 1024
-            rec = [
-                (slab, 0, 0, 0), z, z, (slab, 32 * f, 0, 0), z, z,
-                (slab, 16 * f, 0, 0), z, z, (slab, 32 * f + 512, 0, 0), z, z,
-                (slab, c0, 0, 0), (slab, c0 + 8192, 0, 0), (slab, c0 + 8320, 0, 0), (slab, c0 + 8320 + 128 * self.out_dim, 0, 0),
-            ]  # fmt: skip
-            for i, (kind, o1, o2, cols) in enumerate(rec):
+            for i, (kind, o1, o2, cols) in enumerate(acc_recipe(f, self.out_dim)):
                 t = self._table_acc.recipe[i]
                 t.kind, t.off1, t.off2, t.cols = kind, o1, o2, cols
             self._table_acc.slab_stride = rs
@@ -420,8 +403,6 @@ class FusedTrainStep:
         """Dynamic LDS bytes the accumulating pass takes for this batch: the
         prefetch layout when it fits, else the largest graph's carve plus the
         accumulators."""
-        from deeprank2_amd.fused import lds_for  # noqa: PLC0415
-
         f, out = self.model.input_shape, self.out_dim
         m = self._acc_max_sizes(h)
         if m is not None:
@@ -434,8 +415,6 @@ class FusedTrainStep:
     def _launch_pass(self, h: BatchHandle, p) -> int:
         """The graph pass of a two-launch step: the accumulating pass (returns
         its row count) or the model's per-graph pass (returns 0)."""
-        from deeprank2_amd.fused import lds_for  # noqa: PLC0415
-
         r = self._acc_rows(h)
         if r == 0:
             launch(self.spec, h, self._w, p, wpack=self._packed())
@@ -571,6 +550,46 @@ class FusedTrainStep:
         packed = [] if self.wpack is None else [self.wpack[0]]
         return [*self.params, *[s for st in self.states for s in st], self.counter, self.flat, self.fault, *packed]
 
+    @contextlib.contextmanager
+    def _state_kept(self):
+        """Leaves the training state (``_state_tensors``, ``step_count``) as
+        it was on entry."""
+        snap = [t.detach().clone() for t in self._state_tensors()]
+        n = self.step_count
+        yield
+        for t, s in zip(self._state_tensors(), snap):
+            t.data.copy_(s)
+        self.step_count = n
+
+    def _time_captured(self, launches, n_launches):
+        """``launches(n_launches)`` captured into one HIP graph, replayed once
+        untimed (the first replay uploads the graph) and once between two HIP
+        events on the launch stream: ms per launch."""
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            launches(n_launches)
+        g.replay()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        torch.cuda.synchronize(self.device)
+        return e0.elapsed_time(e1) / n_launches
+
+    def _capture_steps(self, steps):
+        """``steps()`` once eagerly (warm-up: LDS attributes, plans,
+        allocator), then captured into a HIP graph; the state both runs
+        changed is rolled back."""
+        self._packed()  # made before the snapshot, so the restore covers it
+        with self._state_kept():
+            steps()
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                steps()
+            torch.cuda.synchronize(self.device)
+        return g
+
     def capture_sweep(self, handles, global_batch=None):
         """Capture one training step per handle, in order, into ONE HIP graph
         (a sweep over the resident mini-batches): replaying it runs
@@ -578,21 +597,12 @@ class FusedTrainStep:
         left as before the call."""
         for h in handles:
             self._ensure(h.B)
-        self._packed()  # made before the snapshot, so the restore covers it
-        snap = [t.detach().clone() for t in self._state_tensors()]
-        n = self.step_count
-        for h in handles:  # warm-up: LDS attributes, plans, allocator
-            self.step(h, global_batch=global_batch)
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+
+        def steps():
             for h in handles:
                 self.step(h, global_batch=global_batch)
-        torch.cuda.synchronize(self.device)
-        for t, s in zip(self._state_tensors(), snap):
-            t.data.copy_(s)
-        self.step_count = n
-        return g
+
+        return self._capture_steps(steps)
 
     def time_graph_pass(self, handles, n_launches, global_batch=None):
         """Mean duration (ms) of the model's graph pass alone: ``n_launches``
@@ -602,8 +612,6 @@ class FusedTrainStep:
         rocprofv3 kernel average is the cross-check).  State is restored."""
         for h in handles:
             self._ensure(h.B)
-        snap = [t.detach().clone() for t in self._state_tensors()]
-        n = self.step_count
         p = self._pass if (self.spec.dropout > 0 and self.model.dropout > 0) else self._pass_nodrop
 
         def passes(k):
@@ -612,42 +620,23 @@ class FusedTrainStep:
                 p.loss_scale = self.loss_scale(h, global_batch or h.B * self.world)
                 self._launch_pass(h, p)
 
-        passes(len(handles))  # warm-up: LDS attributes, plans
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            passes(n_launches)
-        g.replay()  # untimed replay (first replay uploads the graph)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize(self.device)
-        ms = e0.elapsed_time(e1) / n_launches
-        del g
-        for t, s in zip(self._state_tensors(), snap):
-            t.data.copy_(s)
-        self.step_count = n
-        return ms
+        with self._state_kept():
+            passes(len(handles))  # warm-up: LDS attributes, plans
+            torch.cuda.synchronize(self.device)
+            return self._time_captured(passes, n_launches)
 
     def time_reduce(self, handles, n_launches, global_batch=None):
         """Mean duration (ms) of the step's second launch alone
-        (``dr_reduce_update``: the fixed-order gradient sums + Adam), timed like
-        :meth:`time_graph_pass` (``n_launches`` captured back to back, HIP
-        events on the launch stream).  With the graph pass's time it splits a
-        step into pass / reduce / the rest (launch gaps, host).  State is
-        restored.  None where the step has no separate reduce launch
+        (``dr_reduce_update_opt``: the fixed-order gradient sums + the update),
+        timed like :meth:`time_graph_pass` (``n_launches`` captured back to
+        back, HIP events on the launch stream).  With the graph pass's time it
+        splits a step into pass / reduce / the rest (launch gaps, host).  State
+        is restored.  None where the step has no separate reduce launch
         (data-parallel step, layer-level batches)."""
         if self.pg is not None or any(self.spec.layers is not None and layered.needs_layers(self.spec, h, self.out_dim) for h in handles):
             return None
-        lib = _lib.load()
         for h in handles:
             self._ensure(h.B)
-        snap = [t.detach().clone() for t in self._state_tensors()]
-        n = self.step_count
-        for h in handles:  # one real step each, so the slabs hold a batch's partials
-            self.step(h, global_batch=global_batch)
-        torch.cuda.synchronize(self.device)
 
         def reduces(k):
             stream = _lib.stream_ptr(self.device)  # inside the capture: the capturing stream
@@ -657,21 +646,11 @@ class FusedTrainStep:
                 scale = self.loss_scale(h, global_batch or h.B * self.world)
                 self._reduce(table, slab, self.head.data_ptr(), n_rows, self._upd, self.lpg.data_ptr(), scale, self.loss_out.data_ptr(), stream)
 
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            reduces(n_launches)
-        g.replay()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        g.replay()
-        e1.record()
-        torch.cuda.synchronize(self.device)
-        ms = e0.elapsed_time(e1) / n_launches
-        del g
-        for t, s in zip(self._state_tensors(), snap):
-            t.data.copy_(s)
-        self.step_count = n
-        return ms
+        with self._state_kept():
+            for h in handles:  # one real step each, so the slabs hold a batch's partials
+                self.step(h, global_batch=global_batch)
+            torch.cuda.synchronize(self.device)
+            return self._time_captured(reduces, n_launches)
 
     def capture(self, h: BatchHandle, global_batch=None, dropout=True):
         """Capture one training step on ``h`` into a HIP graph (``torch.cuda.CUDAGraph``).
@@ -684,19 +663,7 @@ class FusedTrainStep:
         ``refresh_packed()`` first.)  Capturing does not change the training
         state (the warm-up step it needs is rolled back)."""
         self._ensure(h.B)
-        self._packed()  # made before the snapshot, so the restore covers it
-        snap = [t.detach().clone() for t in self._state_tensors()]
-        n = self.step_count
-        self.step(h, global_batch=global_batch, dropout=dropout)  # warm-up: LDS attribute, allocator
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self.step(h, global_batch=global_batch, dropout=dropout)
-        torch.cuda.synchronize(self.device)
-        for t, s in zip(self._state_tensors(), snap):
-            t.data.copy_(s)
-        self.step_count = n
-        return g
+        return self._capture_steps(lambda: self.step(h, global_batch=global_batch, dropout=dropout))
 
 
 GINetTrainStep = FusedTrainStep  # GINet's fused spec drives it

@@ -166,6 +166,18 @@ def recipe(f, out):
     ]  # fmt: skip
 
 
+def acc_recipe(f, out):
+    """The accumulating pass's rows (dr_ginet_acc_row_floats): the conv
+    partials as in the per-graph slab, then the head's gradients themselves,
+    summed on chip: fc1.weight, fc1.bias, fc2.weight, fc2.bias."""
+    slab = _lib.DR_GRAD_SLAB
+    fc1w = 32 * f + 1024  # after the conv partials
+    fc1b = fc1w + 128 * 64
+    fc2w = fc1b + 128
+    fc2b = fc2w + 128 * out
+    return [*recipe(f, out)[:12], (slab, fc1w, 0, 0), (slab, fc1b, 0, 0), (slab, fc2w, 0, 0), (slab, fc2b, 0, 0)]
+
+
 def weights_c(params):
     w = _lib.GinetWeightsC()
     w.w1, w.w1e = params[0].data_ptr(), params[6].data_ptr()

@@ -649,7 +649,7 @@ int dr_reduce_update(const dr_param_table* t, const float* slab, const float* he
                      const dr_adam* adam, const float* loss_per_graph, float loss_scale, float* loss_out,
                      void* stream);
 
-/* The same launch with the update rule chosen by kind (reduce_optim.hip; one
+/* The same launch with the update rule chosen by kind (reduce.hip; one
  * kernel instantiation per kind, picked on the host).  Everything dr_adam
  * carries holds for every kind: step_counter, fault, grad_div, mirror /
  * mirror_idx, fault_clear / ticket, enabled.  Rules as torch 2.10's

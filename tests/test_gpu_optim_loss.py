@@ -3,12 +3,14 @@
 DR_LOSS_SMOOTH_L1 / DR_LOSS_HUBER in every graph pass): the update rules
 against torch's optimizers, the losses against the CPU oracle
 (oracle/gnn_ref.py) plus torch's loss functions, and the Trainer end to end
-on the reference's documented ``configure_optimizers(torch.optim.Adamax, ...)``.
+on the reference's documented ``configure_optimizers(torch.optim.Adamax, ...)``;
+last, the reduce launch alone on a synthetic table (section 7).
 Tolerances: 1e-4 on outputs / losses / gradients (north_star, fp32), rtol
 1e-5 + atol 1e-7 on the update (test_gpu_ginet.py's figure)."""
 
 from __future__ import annotations
 
+import ctypes
 import functools
 
 import numpy as np
@@ -17,6 +19,7 @@ import torch
 from _util import assert_grad_close
 from torch import nn
 
+from deeprank2_amd import _lib
 from deeprank2_amd.dataset import GraphDataset
 from deeprank2_amd.engine import FusedTrainStep
 from deeprank2_amd.exporters import MemoryOutputExporter
@@ -492,3 +495,182 @@ def test_adamax_after_allreduce_matches_the_single_process_step(tmp_path):
         np.testing.assert_allclose(a.detach().cpu().numpy(), b.detach().cpu().numpy(), err_msg=n, **UPD)
         np.testing.assert_allclose(ma.cpu().numpy(), mb.cpu().numpy(), err_msg=n, **UPD)
         np.testing.assert_allclose(ua.cpu().numpy(), ub.cpu().numpy(), err_msg=n, **UPD)
+
+
+# ------------------------------------------------ 7. the reduce launch on its own
+# A synthetic table through ctypes, no model.  (numel, kind, off1, off2, cols):
+# numel 1 / 65 / 512 give a block a partial, a straddling and a full 64-element
+# tile; every recipe kind occurs, OUTER with 64 columns.
+_Z, _SLAB, _OUTER, _HEAD = _lib.DR_GRAD_ZERO, _lib.DR_GRAD_SLAB, _lib.DR_GRAD_OUTER, _lib.DR_GRAD_HEAD
+RT_PARAMS = [
+    (65, _SLAB, 0, 0, 0), (1, _Z, 0, 0, 0), (512, _OUTER, 0, 8, 64), (1, _HEAD, 72, 0, 0),
+    (512, _SLAB, 65, 0, 0), (65, _HEAD, 73, 0, 0), (65, _OUTER, 0, 8, 64), (65, _Z, 0, 0, 0),
+]  # fmt: skip
+RT_SLAB_STRIDE, RT_HEAD_STRIDE = 580, 140
+# (n_batch, slab_rows): chunks of fewer than 8 rows and empty ones; the
+# 24-row tail loop; 270 slab rows, more than one 24-row group per chunk
+RT_BATCHES = [(5, 1), (70, 1), (90, 3)]
+RT_ADAM = dict(lr=1e-2, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2)
+
+
+def _rt_columns_fit():
+    for n, kind, o1, o2, cols in RT_PARAMS:
+        if kind == _SLAB:
+            assert o1 + n <= RT_SLAB_STRIDE
+        elif kind == _HEAD:
+            assert o1 + n <= RT_HEAD_STRIDE
+        elif kind == _OUTER:
+            assert o1 + (n + cols - 1) // cols <= RT_HEAD_STRIDE and o2 + cols <= RT_HEAD_STRIDE
+
+
+@functools.lru_cache(maxsize=None)
+def _rt_partials(n_batch, slab_rows):
+    """Seeded per-graph partials on the host: slab rows, head rows, loss terms."""
+    g = torch.Generator().manual_seed(1000 * n_batch + slab_rows)
+    slab = torch.randn(n_batch * slab_rows, RT_SLAB_STRIDE, generator=g)
+    head = torch.randn(n_batch, RT_HEAD_STRIDE, generator=g)
+    return slab, head, torch.rand(n_batch, generator=g)
+
+
+class ReduceState:
+    """Device buffers one reduce run owns (the same seeded start for every
+    run): parameters, moments, gradients, step counter, loss, fault flag."""
+
+    def __init__(self):
+        g = torch.Generator().manual_seed(5)
+        numel = [p[0] for p in RT_PARAMS]
+        self.p = [torch.randn(n, generator=g).to(DEV) for n in numel]
+        self.m = [(0.1 * torch.randn(n, generator=g)).to(DEV) for n in numel]
+        self.v = [(0.01 * torch.rand(n, generator=g)).to(DEV) for n in numel]
+        self.g = [torch.randn(n, generator=g).to(DEV) for n in numel]
+        self.counter = torch.zeros(2, dtype=torch.int64, device=DEV)
+        self.loss = torch.full((1,), 8.0, device=DEV)
+        self.fault = torch.zeros(1, dtype=torch.int32, device=DEV)
+        self.div = torch.full((1,), 4.0, device=DEV)
+
+    def table(self, slab_rows):
+        t = _lib.ParamTableC()
+        for i, (n, kind, o1, o2, cols) in enumerate(RT_PARAMS):
+            t.param[i], t.grad[i] = self.p[i].data_ptr(), self.g[i].data_ptr()
+            t.exp_avg[i], t.exp_avg_sq[i] = self.m[i].data_ptr(), self.v[i].data_ptr()
+            t.numel[i] = n
+            t.recipe[i] = _lib.GradRecipeC(kind, o1, o2, cols)
+        t.n_params, t.slab_stride, t.head_stride, t.slab_rows = len(RT_PARAMS), RT_SLAB_STRIDE, RT_HEAD_STRIDE, slab_rows
+        return t
+
+    def adam(self, grad_div=False):
+        a = _lib.AdamC()
+        a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = (RT_ADAM[k] for k in ("lr", "beta1", "beta2", "eps", "weight_decay"))
+        a.enabled = 1
+        a.step_counter, a.fault = self.counter.data_ptr(), self.fault.data_ptr()
+        if grad_div:
+            a.grad_div = self.div.data_ptr()
+        return a
+
+    def host(self):
+        torch.cuda.synchronize()
+        cat = lambda ts: torch.cat([t.cpu() for t in ts])  # noqa: E731
+        return {"param": cat(self.p), "exp_avg": cat(self.m), "exp_avg_sq": cat(self.v), "grad": cat(self.g), "loss": self.loss.cpu(), "counter": self.counter.cpu()}
+
+
+def reduce_call(lib, entry, kind, table, slab, head, n_batch, adam, lpg, scale, loss):
+    """One reduce launch on the current stream.  entry: "adam" =
+    dr_reduce_update; "opt" / "opt_om" = dr_reduce_update_opt with om_beta* 0 /
+    fl(1 - beta) rounded from double."""
+    stream = _lib.stream_ptr(torch.device(DEV))
+    if entry == "adam":
+        assert kind == _lib.DR_OPT_ADAM
+        rc = lib.dr_reduce_update(ctypes.byref(table), _lib.ptr(slab), _lib.ptr(head), n_batch, ctypes.byref(adam), _lib.ptr(lpg), scale, _lib.ptr(loss), stream)
+    else:
+        om = (0.0, 0.0) if entry == "opt" else (1.0 - RT_ADAM["beta1"], 1.0 - RT_ADAM["beta2"])
+        opt = _lib.OptimC(adam, kind, *om, 0)
+        rc = lib.dr_reduce_update_opt(ctypes.byref(table), _lib.ptr(slab), _lib.ptr(head), n_batch, ctypes.byref(opt), _lib.ptr(lpg), scale, _lib.ptr(loss), stream)
+    assert rc == 0, (entry, kind, rc)
+
+
+def reduce_three_steps(lib, entry, kind, n_batch, slab_rows):
+    """Three steps from the seeded start on the (n_batch, slab_rows) partials,
+    the step number taken from the device counter: every output, on the host."""
+    _rt_columns_fit()
+    slab, head, lpg = (x.to(DEV) for x in _rt_partials(n_batch, slab_rows))
+    st = ReduceState()
+    table, adam = st.table(slab_rows), st.adam()
+    for _ in range(3):
+        st.counter[1].copy_(st.counter[0])  # the snapshot a graph pass takes
+        reduce_call(lib, entry, kind, table, slab, head, n_batch, adam, lpg, 1.0 / n_batch, st.loss)
+    return st.host()
+
+
+def _bits(t):
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+@pytest.mark.parametrize(("n_batch", "slab_rows"), RT_BATCHES)
+def test_reduce_launch_adam_entries_agree_and_sum_within_the_fp32_bound(n_batch, slab_rows):
+    lib = _lib.load()
+    ref = reduce_three_steps(lib, "adam", _lib.DR_OPT_ADAM, n_batch, slab_rows)
+    for entry in ("opt", "opt_om"):  # the Adam kernel forms 1.f - beta itself, whatever om_beta* holds
+        out = reduce_three_steps(lib, entry, _lib.DR_OPT_ADAM, n_batch, slab_rows)
+        for k, v in ref.items():
+            assert torch.equal(_bits(out[k]), _bits(v)), (entry, k)
+    assert ref["counter"][0] == 3
+    start = ReduceState().host()
+    assert not torch.equal(ref["param"], start["param"])
+    # each gradient against a float64 sum of the same partials: fp32 recursive
+    # summation of nb terms is within nb * 2^-24 * sum|terms| of the exact sum
+    slab, head, lpg = (x.double() for x in _rt_partials(n_batch, slab_rows))
+    u, lo = 2.0**-24, 0
+    for n, kind, o1, o2, cols in RT_PARAMS:
+        got = ref["grad"][lo : lo + n].double()
+        lo += n
+        if kind == _Z:
+            assert not got.any()
+            continue
+        if kind == _SLAB:
+            terms = slab[:, o1 : o1 + n]
+        elif kind == _HEAD:
+            terms = head[:, o1 : o1 + n]
+        else:
+            e = torch.arange(n)
+            terms = head[:, o1 + e // cols] * head[:, o2 + e % cols]
+        bound = terms.shape[0] * u * terms.abs().sum(0)
+        err = (got - terms.sum(0)).abs()
+        print(f"reduce n_batch={n_batch} slab_rows={slab_rows} kind={kind} numel={n}: max err/bound {float((err / bound).max()):.3g}")
+        assert (err <= bound).all(), (kind, n)
+    scale = 1.0 / n_batch  # the loss: n_batch - 1 additions and the scaling
+    assert abs(float(ref["loss"]) - float(lpg.sum()) * scale) <= (n_batch + 1) * u * float(lpg.abs().sum()) * scale
+
+
+def test_reduce_launch_divides_supplied_gradients_and_loss():
+    """slab == head == NULL with grad_div: the gradients in the table and the
+    loss already in loss_out are divided (by 4: exact), then the update runs.
+    Three steps."""
+    st = ReduceState()
+    start = st.host()
+    table, adam = st.table(1), st.adam(grad_div=True)
+    for _ in range(3):
+        st.counter[1].copy_(st.counter[0])
+        reduce_call(_lib.load(), "opt", _lib.DR_OPT_ADAM, table, None, None, 0, adam, None, 1.0, st.loss)
+    out = st.host()
+    assert torch.equal(out["grad"], start["grad"] / 64.0)  # three launches, each divides what it finds
+    assert float(out["loss"]) == float(start["loss"]) / 64.0
+    assert out["counter"][0] == 3 and not torch.equal(out["param"], start["param"])
+
+
+def test_reduce_launch_with_fault_flag_reports_nan_and_keeps_state():
+    """*fault = 1 (the flag a graph pass sets when it gives up a hand-off; a
+    value, not a device fault): NaN loss and gradients, nothing updated."""
+    n_batch, slab_rows = RT_BATCHES[1]
+    slab, head, lpg = (x.to(DEV) for x in _rt_partials(n_batch, slab_rows))
+    st = ReduceState()
+    start = st.host()
+    st.fault.fill_(1)
+    table, adam = st.table(slab_rows), st.adam()
+    for _ in range(3):
+        st.counter[1].copy_(st.counter[0])
+        reduce_call(_lib.load(), "opt", _lib.DR_OPT_ADAM, table, slab, head, n_batch, adam, lpg, 1.0 / n_batch, st.loss)
+    out = st.host()
+    assert torch.isnan(out["loss"]).all() and torch.isnan(out["grad"]).all()
+    for k in ("param", "exp_avg", "exp_avg_sq"):
+        assert torch.equal(out[k], start[k]), k
+    assert out["counter"][0] == 0
