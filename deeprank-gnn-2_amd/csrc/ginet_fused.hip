@@ -25,6 +25,10 @@
 // depth-0 max pool routes each channel's gradient to one member per cluster,
 // the conv1 weight gradient is sum_k v_k·Z[arg_k] and the backward needs no
 // gather over the edges at all.
+// Z depends only on the store's x and CSR, so by default it is built once per
+// store (dr_aggregate_x) and the Z-input kernels (graph_body<..., ZIN>) DMA each
+// graph's block into LDS instead of staging x / col / rowptr and gathering; the
+// gather kernels stay as the fallback (no array yet, DR_GINET_AGGX=0).
 // Roofline: HBM-bound on the compulsory inputs (x, CSR, clusters) and the
 // per-graph partial writes — see DESIGN.md §Roofline.
 
@@ -49,6 +53,9 @@ namespace {
 #endif
 #ifndef DR_TILE_STORE_WAIT
 #define DR_TILE_STORE_WAIT 0  // 1: the tile kernels wait for their Z stores before the MFMA phase (r05 form, A/B)
+#endif
+#ifndef DR_ZIN_EARLY_W
+#define DR_ZIN_EARLY_W 1  // Z-input kernels: conv2 / head weights requested with the staging DMA (0: after the staging barrier, as the gather kernels; A/B)
 #endif
 #ifndef DR_DMA_ROT
 #define DR_DMA_ROT 0  // 1: spread starting waves (measured 0.1 us slower per pass, r05)
@@ -75,7 +82,10 @@ struct Carve {
 // row stride XS = r4(F) (16-byte rows for the DMA and the float4 gather);
 // Z = A·X uses the stride KP+2 so the MFMA column reads are bank-conflict
 // free.
-__host__ __device__ inline Carve carve(int N, int E, int F, int K0, int P1, int K1, int alias, int OUT) {
+// zs > 0: the Z-input form (dr_ginet_graph_pass_z): Z = A·X arrives from the
+// store's array with rows of zs words, the stride it keeps in LDS, and the X,
+// row pointer and column regions go.
+__host__ __device__ inline Carve carve(int N, int E, int F, int K0, int P1, int K1, int alias, int OUT, int zs = 0) {
   Carve c;
   // K padded to the kernel's KPT (32 for F <= 32, else 64: the MFMA steps it
   // runs; zeros past F).  (Until r05 KP was r16(F), shorter than KPT for F <= 16
@@ -83,19 +93,24 @@ __host__ __device__ inline Carve carve(int N, int E, int F, int K0, int P1, int 
   // row pointers being DMA'd beside it, and the last k steps read other
   // waves' rows.)
   c.KP = F <= 32 ? 32 : 64;
-  c.LDW = c.KP + 2;   // rows 2 words apart: lanes (row li, k+kq) hit 32 distinct banks
+  c.LDW = zs > 0 ? zs : c.KP + 2;   // rows 2 words apart: lanes (row li, k+kq) hit 32 distinct banks
   c.XS = r4(F);
+  c.x = c.rp = c.col = 0;
   int o = 0;
 #define TAKE(field, words) \
-  c.field = o;             \
-  o += r4(words);
+  {                        \
+    c.field = o;           \
+    o += r4(words);        \
+  }
   TAKE(w1, 32 * F)           // [W1; W1e] (conv1 / conv1_ext .fc.weight), rows of F
   TAKE(w2, 1024)             // [W2 | W2e] (conv2 / conv2_ext .fc.weight)
   TAKE(fc2, OUT * 128 + OUT) // fc2.weight rows, then fc2.bias
-  TAKE(x, N * c.XS)
+  if (zs <= 0) TAKE(x, N * c.XS)
   TAKE(z, N * c.LDW)
-  TAKE(rp, N + 1)
-  TAKE(col, (E + 1) / 2)     // uint16 column ids
+  if (zs <= 0) {
+    TAKE(rp, N + 1)
+    TAKE(col, (E + 1) / 2)   // uint16 column ids
+  }
   TAKE(cl0, N)               // depth-0 cluster of each node
   TAKE(key, 2 * K0 * 32)     // depth-0 pooling keys (uint64)
   TAKE(p1, K0 * 32)
@@ -138,22 +153,29 @@ struct AccLayout {
 };
 
 __host__ __device__ inline Carve carve_acc(int N, int E, int F, int K0, int P1, int K1, int alias, int OUT,
-                                           const AccLayout& L, int par) {
+                                           const AccLayout& L, int par, int zs = 0) {
   Carve c;
   c.KP = F <= 32 ? 32 : 64;  // as carve()
-  c.LDW = c.KP + 2;
+  c.LDW = zs > 0 ? zs : c.KP + 2;
   c.XS = r4(F);
+  c.x = c.rp = c.col = 0;
   int o = 0;
 #define TAKE(field, words) \
-  c.field = o;             \
-  o += r4(words);
+  {                        \
+    c.field = o;           \
+    o += r4(words);        \
+  }
   TAKE(w1, 32 * F)
   TAKE(w2, 1024)
   TAKE(fc2, OUT * 128 + OUT)
   o = par ? L.in1 : L.in0;
-  TAKE(x, N * c.XS)
-  TAKE(rp, N + 1)
-  TAKE(col, (E + 1) / 2)
+  if (zs > 0) {  // Z is an input: one copy per parity, the next graph's DMA'd under this graph's tail
+    TAKE(z, N * c.LDW)
+  } else {
+    TAKE(x, N * c.XS)
+    TAKE(rp, N + 1)
+    TAKE(col, (E + 1) / 2)
+  }
   TAKE(cl0, N)
   TAKE(p1rp, K0 + 1)
   TAKE(p1c, P1)
@@ -167,7 +189,7 @@ __host__ __device__ inline Carve carve_acc(int N, int E, int F, int K0, int P1, 
   TAKE(m1p, K1 + 1)
   TAKE(m1i, K0)
   o = L.scr;
-  TAKE(z, N * c.LDW)
+  if (zs <= 0) TAKE(z, N * c.LDW)
   TAKE(key, 2 * K0 * 32)
   TAKE(p1, K0 * 32)
   TAKE(a1, K0 * 32)
@@ -186,15 +208,16 @@ __host__ __device__ inline Carve carve_acc(int N, int E, int F, int K0, int P1, 
 }
 
 // the layout for the batch maxima (every graph's carve_acc fits inside it)
-__host__ __device__ inline AccLayout acc_layout(int Nm, int Em, int F, int K0m, int P1m, int K1m, int alias, int OUT) {
+__host__ __device__ inline AccLayout acc_layout(int Nm, int Em, int F, int K0m, int P1m, int K1m, int alias, int OUT,
+                                                int zs = 0) {
   AccLayout L;
   L.in0 = r4(32 * F) + 1024 + r4(OUT * 128 + OUT);
-  const int XS = r4(F), LDW = (F <= 32 ? 32 : 64) + 2;
-  const int in = r4(Nm * XS) + r4(Nm + 1) + r4((Em + 1) / 2) + r4(Nm) + r4(K0m + 1) + r4(P1m) +
+  const int XS = r4(F), LDW = zs > 0 ? zs : (F <= 32 ? 32 : 64) + 2;
+  const int in = (zs > 0 ? r4(Nm * LDW) : r4(Nm * XS) + r4(Nm + 1) + r4((Em + 1) / 2)) + r4(Nm) + r4(K0m + 1) + r4(P1m) +
                  (alias ? 0 : r4(K0m + 1) + r4(P1m)) + r4(K1m + 1) + r4(K0m);
   L.in1 = L.in0 + in;
   L.scr = L.in1 + in;
-  L.total = L.scr + r4(Nm * LDW) + r4(2 * K0m * 32) + 3 * r4(K0m * 32) + 2 * r4(K0m * 64) + 2 * r4(K1m * 64) + r4(K0m) +
+  L.total = L.scr + (zs > 0 ? 0 : r4(Nm * LDW)) + r4(2 * K0m * 32) + 3 * r4(K0m * 32) + 2 * r4(K0m * 64) + 2 * r4(K1m * 64) + r4(K0m) +
             r4(HEADW) + r4(NW * 64) + r4(32);
   return L;
 }
@@ -205,6 +228,10 @@ struct GinetArgs {
   dr_pass p;
   const dr_graph_desc* descs;
   int32_t B;
+  // the Z-input kernels (dr_ginet_graph_pass_z / dr_ginet_acc_pass_z): the
+  // store-wide Z = A·X of dr_aggregate_x, node i of the store at z + i * z_stride
+  int32_t z_stride = 0;
+  const float* z = nullptr;
 };
 
 // torch relu keeps NaN (clamp_min propagates it); its backward masks where
@@ -823,7 +850,12 @@ struct AccCtx {
 // KPT: conv1's K (F) padded to whole 16-deep MFMA steps, 32 (F <= 32) or 64.
 // ACC / PF: the accumulating pass (AccCtx) and its prefetch layout.  Returns
 // the step counter value the pass used (its dropout offset).
-template <int KPT, bool ACC = false, bool PF = false>
+// ZIN: Z = A·X comes from the store-wide array of dr_aggregate_x (a.z, rows of
+// a.z_stride words, the LDS row stride too): the graph's block is DMA'd into
+// sZ in the place of x, the column ids and the row pointers, and the gather
+// and the zeroing of Z's K padding are compiled out (the array holds the same
+// bits the gather would write, zeros past F).  From the MFMA on, the same code.
+template <int KPT, bool ACC = false, bool PF = false, bool ZIN = false>
 __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx& ac) {
   extern __shared__ __attribute__((aligned(16))) float lds_raw[];
   float* lds = lds_raw + (ACC ? ac.acc_words : 0);
@@ -849,7 +881,8 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
                "s"(s.p1t_rowptr), "s"(s.p1t_col), "s"(s.m1_ptr), "s"(s.m1_idx), "s"(s.y), "s"(F), "s"(alias),
                "s"(OUT), "s"(n0), "s"(ec0), "s"(k00), "s"(q0), "s"(k10), "s"(N), "s"(E), "s"(K0), "s"(P1), "s"(K1),
                "s"(g));
-  const Carve c = PF ? carve_acc(N, E, F, K0, P1, K1, alias, OUT, ac.lay, ac.par) : carve(N, E, F, K0, P1, K1, alias, OUT);
+  const int zs = ZIN ? a.z_stride : 0;
+  const Carve c = PF ? carve_acc(N, E, F, K0, P1, K1, alias, OUT, ac.lay, ac.par, zs) : carve(N, E, F, K0, P1, K1, alias, OUT, zs);
   const int LDW = c.LDW, XS = c.XS;
 
   float* sW1 = lds + c.w1;
@@ -889,6 +922,21 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
 #pragma unroll
     for (int j = 0; j < 8; ++j) fc1_col[j] = a.w.fc1w[(rcc * 8 + j) * 64 + o];
   };
+  float wv2, wfc[3];
+  auto load_head_weights = [&]() {
+    wv2 = (tid < 512) ? a.w.w2[tid] : a.w.w2e[tid - 512];
+    const int nf = OUT * 128;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const int p = tid + u * NT;
+      wfc[u] = 0.f;
+      if (p < nf) wfc[u] = a.w.fc2w[p];
+      else if (p < nf + OUT) wfc[u] = a.w.fc2b[p - nf];
+    }
+    // fc1 last: the wait for W2 / fc2 before their LDS stores (end of the
+    // front half) then leaves these 11 loads in flight (vmcnt counts in order)
+    load_fc1();
+  };
   // (ACC: scalar loads through the constant address space — read-only for the
   // launch; hipcc cannot prove that in the accumulating loop and would use a
   // vector load, waited for by the staging's vmcnt(0))
@@ -900,9 +948,14 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   auto stage_inputs = [&](const dr_graph_desc& dd, const Carve& cc) {
     const int64_t dn0 = dd.node0, dk00 = dd.k0;
     const int dg = dd.gid, dN = dd.n_nodes, dK0 = dd.n_k0;
-    dma_x4_async(lds + cc.x, s.x + dn0 * (int64_t)XS, dN * XS / 4, tid);
-    dma_x4_async(lds + cc.col, s.col + dd.col0, (dd.n_edges + 7) / 8, tid, 7);
-    dma_words_async(lds + cc.rp, s.rowptr + dn0 + dg, dN + 1, tid, 13);
+    if (ZIN) {  // the graph's Z block as it lies in HBM (16-byte lanes where the stride gives 16-byte rows)
+      if ((LDW & 3) == 0) dma_x4_async(lds + cc.z, a.z + dn0 * (int64_t)LDW, dN * LDW / 4, tid);
+      else dma_words_async(lds + cc.z, a.z + dn0 * (int64_t)LDW, dN * LDW, tid);
+    } else {
+      dma_x4_async(lds + cc.x, s.x + dn0 * (int64_t)XS, dN * XS / 4, tid);
+      dma_x4_async(lds + cc.col, s.col + dd.col0, (dd.n_edges + 7) / 8, tid, 7);
+      dma_words_async(lds + cc.rp, s.rowptr + dn0 + dg, dN + 1, tid, 13);
+    }
     dma_words_async(lds + cc.cl0, s.cl0 + dn0, dN, tid, 3);
     dma_words_async(lds + cc.p1rp, s.p1_rowptr + dk00 + dg, dK0 + 1, tid, 10);
     dma_words_async(lds + cc.p1c, s.p1_col + dd.p1, dd.n_p1, tid, 11);
@@ -914,9 +967,14 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
     dma_words_async(lds + cc.m1i, s.m1_idx + dk00, dK0, tid, 1);
   };
   if (!PF) {  // (DR_DMA_ROT = 1: starting waves spread over the copies; measured slower)
-    dma_x4(sX, s.x + n0 * (int64_t)XS, N * XS / 4, tid);
-    dma_x4(scol, s.col + ec0, (E + 7) / 8, tid, DR_DMA_ROT * 7);
-    dma_words(srp, s.rowptr + n0 + g, N + 1, tid, DR_DMA_ROT * 13);
+    if (ZIN) {
+      if ((LDW & 3) == 0) dma_x4(sZ, a.z + n0 * (int64_t)LDW, N * LDW / 4, tid);
+      else dma_words(sZ, a.z + n0 * (int64_t)LDW, N * LDW, tid);
+    } else {
+      dma_x4(sX, s.x + n0 * (int64_t)XS, N * XS / 4, tid);
+      dma_x4(scol, s.col + ec0, (E + 7) / 8, tid, DR_DMA_ROT * 7);
+      dma_words(srp, s.rowptr + n0 + g, N + 1, tid, DR_DMA_ROT * 13);
+    }
     dma_words(scl0, s.cl0 + n0, N, tid, DR_DMA_ROT * 3);
     dma_words(sp1rp, s.p1_rowptr + k00 + g, K0 + 1, tid, DR_DMA_ROT * 10);
     dma_words(sp1c, s.p1_col + q0, P1, tid, DR_DMA_ROT * 11);
@@ -933,12 +991,19 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
     dma_words(sW1, a.w.w1, 16 * F, tid, DR_DMA_ROT * 5);  // [W1; W1e] rows of F, packed
     dma_words(sW1 + 16 * F, a.w.w1e, 16 * F, tid, DR_DMA_ROT * 14);
   }
+  // ZIN: the front half is too short to cover the head weights' latency (it
+  // showed as a wait before W2's and fc2's LDS stores), so they are requested
+  // here, beside the staging DMA, and arrive with it: 10.50 -> 10.25 us per
+  // pass.  (Only W2 / fc2 here and fc1's 64 KB of registers after the barrier:
+  // 10.6 us, profiles/r07.)
+  if (ZIN && DR_ZIN_EARLY_W) load_head_weights();
   {  // zero Z's K padding (cols XS..KPT; X's own pad is zero) and the pooling keys
-    const int padz = KPT - XS;  // (rows are KP = KPT wide, carve)
-    for (int p = tid; p < N * padz; p += NT) {
-      const int i = p / padz;
-      sZ[i * LDW + XS + (p - i * padz)] = 0.f;
-    }
+    const int padz = KPT - XS;  // (rows are KP = KPT wide, carve; ZIN: the array's rows arrive whole)
+    if (!ZIN)
+      for (int p = tid; p < N * padz; p += NT) {
+        const int i = p / padz;
+        sZ[i * LDW + XS + (p - i * padz)] = 0.f;
+      }
     for (int p = tid; p < K0 * 32; p += NT) skey[p] = 0ull;
     if (tid < 64) lds[c.p2 + tid] = 0.f;  // (TailLds::p2_zeroed)
   }
@@ -955,22 +1020,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   // VGPRs now and store them to LDS after the front half, so their latency
   // overlaps it.  (An LDS DMA here would make hipcc wait for it before every
   // LDS read.)
-  float wv2, wfc[3];
-  auto load_head_weights = [&]() {
-    wv2 = (tid < 512) ? a.w.w2[tid] : a.w.w2e[tid - 512];
-    const int nf = OUT * 128;
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      const int p = tid + u * NT;
-      wfc[u] = 0.f;
-      if (p < nf) wfc[u] = a.w.fc2w[p];
-      else if (p < nf + OUT) wfc[u] = a.w.fc2b[p - nf];
-    }
-    // fc1 last: the wait for W2 / fc2 before their LDS stores (end of the
-    // front half) then leaves these 11 loads in flight (vmcnt counts in order)
-    load_fc1();
-  };
-  load_head_weights();
+  if (!(ZIN && DR_ZIN_EARLY_W)) load_head_weights();
   // ---------------- conv1 + depth-0 pooling, one 16-row tile per wave -------
   // Each wave runs its rows through the whole front half with no workgroup
   // barrier in between:
@@ -1006,7 +1056,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
       wa[j] = kk < F ? sW1[li * F + kk] : 0.f;
       wb[j] = kk < F ? sW1[(16 + li) * F + kk] : 0.f;
     }
-    if (PF) {  // the waves with no tile stage the next graph's inputs into the other buffer
+    if (PF && !ZIN) {  // the waves with no tile stage the next graph's inputs into the other buffer
       const int busy = (N + 15) >> 4;
       if (ac.next >= 0 && busy < NW && wave >= busy) {
         const dr_graph_desc dn = desc_scalar(a.descs + ac.next);
@@ -1031,6 +1081,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
     }
     for (int tt = wave; tt * 16 < N; tt += NW) {
       const int r0 = tt * 16;
+      if (!ZIN) {
 #if DR_GATHER_ROW2
       if (nch <= 8) {  // one row per lane (r0 + lane/4), chunks q and q ^ 4 (q = lane%4, or +4 on odd rows)
         const int i = r0 + (lane >> 2);
@@ -1082,6 +1133,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
       }
       // this wave's Z rows are complete in LDS before its own MFMA reads them
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      }  // (ZIN: Z was staged whole, before the barrier)
       if (tt == 0) STAMP(20);  // (wave 0's first tile: gather done)
       const int ar = min(r0 + li, N - 1);  // rows past N compute garbage that is never pooled
       floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -1134,6 +1186,18 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
     for (int u = 0; u < 3; ++u)
       if (tid + u * NT < nf) sFc2[tid + u * NT] = wfc[u];
   }
+  if (PF && ZIN) {
+    // With no gather the front half is a few hundred cycles per wave and no
+    // wave idles through it, so every wave issues its share of the next
+    // graph's inputs, after its own tile and the weight stores above (whose
+    // wait for their loads would otherwise take these copies in): the copies
+    // land under this graph's tail.
+    if (ac.next >= 0) {
+      const dr_graph_desc dn = desc_scalar(a.descs + ac.next);
+      stage_inputs(dn, carve_acc(dn.n_nodes, dn.n_edges, F, dn.n_k0, dn.n_p1, dn.n_k1, alias, OUT, ac.lay, ac.par ^ 1, zs));
+    }
+    if (tid == 0) *ac.staged = ac.next >= 0 ? 1u : 0u;
+  }
   STAMP(2);
   __syncthreads();
   STAMP(3);
@@ -1159,12 +1223,12 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   return drop_offset;
 }
 
-template <int KPT>
+template <int KPT, bool ZIN = false>
 __global__ void __launch_bounds__(NT) ginet_graph_kernel(GinetArgs a) {
 #ifdef DR_STAMPS  // cross-kernel timeline (s_memrealtime, 100 MHz chip clock): slots 30 / 31 = entry / exit
   if (threadIdx.x == 0 && a.p.stamps) a.p.stamps[(int64_t)blockIdx.x * 32 + 30] = __builtin_amdgcn_s_memrealtime();
 #endif
-  graph_body<KPT>(a, AccCtx{});
+  graph_body<KPT, false, false, ZIN>(a, AccCtx{});
 #ifdef DR_STAMPS
   if (threadIdx.x == 0 && a.p.stamps) a.p.stamps[(int64_t)blockIdx.x * 32 + 31] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1194,7 +1258,7 @@ __host__ __device__ inline int acc_words(int F, int OUT, bool fc1_in_lds) {
   return 32 * F + 1024 + acc_head_words(OUT) + (fc1_in_lds ? 128 * 64 : 0);
 }
 
-template <int KPT, bool PF>
+template <int KPT, bool PF, bool ZIN = false>
 __global__ void __launch_bounds__(NT) ginet_acc_kernel(GinetArgs a, const int32_t* plan, AccLayout lay) {
   extern __shared__ __attribute__((aligned(16))) float lds_raw[];
   const int F = a.s.n_feat, OUT = a.p.out_dim, tid = threadIdx.x;
@@ -1228,7 +1292,7 @@ __global__ void __launch_bounds__(NT) ginet_acc_kernel(GinetArgs a, const int32_
     typedef const __attribute__((address_space(4))) GinetArgs* KArgs;
     KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("; dr_kargs" : "+s"(ka));
-    graph_body<KPT, true, PF>(*(const GinetArgs*)ka, ac);
+    graph_body<KPT, true, PF, ZIN>(*(const GinetArgs*)ka, ac);
     __syncthreads();  // the graph carve is restaged by the next graph
   }
   // the workgroup's row, then its loss sum
@@ -1796,8 +1860,10 @@ __host__ __device__ inline TailCarve tail_carve(int K0, int P1, int K1, int alia
   TailCarve c;
   int o = 0;
 #define TAKE(field, words) \
-  c.field = o;             \
-  o += r4(words);
+  {                        \
+    c.field = o;           \
+    o += r4(words);        \
+  }
   TAKE(w2, 1024)
   TAKE(fc2, OUT * 128 + OUT)
   TAKE(p1, K0 * 32)
@@ -1962,9 +2028,10 @@ extern "C" int64_t dr_ginet_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t 
   return 4LL * carve(n_nodes, n_edges, n_feat, k0, p1_edges, k1, transpose_aliased, out_dim).total;
 }
 
-extern "C" int dr_ginet_graph_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
-                                   const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes,
-                                   void* stream) {
+// dr_ginet_graph_pass (z = null) and dr_ginet_graph_pass_z
+static int graph_pass_launch(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                             const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes, const float* z,
+                             int32_t z_stride, void* stream) {
   if (!store || !descs || !w || !pass || n_batch < 0) return DR_E_ARG;
   DR_CHECK(dr_check_loss(pass));
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
@@ -1984,14 +2051,48 @@ extern "C" int dr_ginet_graph_pass(const dr_graph_store* store, const dr_graph_d
   args.p = *pass;
   args.descs = descs;
   args.B = n_batch;
+  args.z = z;
+  args.z_stride = z_stride;
+#define DR_GRAPH_LAUNCH(KPT, ZIN)                                                                                   \
+  do {                                                                                                              \
+    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_graph_kernel<KPT, ZIN>)));                       \
+    hipLaunchKernelGGL((ginet_graph_kernel<KPT, ZIN>), dim3(n_batch), dim3(NT), lds_bytes, (hipStream_t)stream, args); \
+  } while (0)
   if (store->n_feat <= 32) {
-    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_graph_kernel<32>)));
-    hipLaunchKernelGGL(ginet_graph_kernel<32>, dim3(n_batch), dim3(NT), lds_bytes, (hipStream_t)stream, args);
+    if (z) DR_GRAPH_LAUNCH(32, true);
+    else DR_GRAPH_LAUNCH(32, false);
   } else {
-    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_graph_kernel<64>)));
-    hipLaunchKernelGGL(ginet_graph_kernel<64>, dim3(n_batch), dim3(NT), lds_bytes, (hipStream_t)stream, args);
+    if (z) DR_GRAPH_LAUNCH(64, true);
+    else DR_GRAPH_LAUNCH(64, false);
   }
+#undef DR_GRAPH_LAUNCH
   return (int)hipGetLastError();
+}
+
+extern "C" int dr_ginet_graph_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                                   const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes,
+                                   void* stream) {
+  return graph_pass_launch(store, descs, n_batch, w, pass, lds_bytes, nullptr, 0, stream);
+}
+
+// a usable Z array: rows at least the kernel's K wide, and 8-byte aligned (stride even)
+static bool z_args_ok(const dr_graph_store* store, const float* z, int32_t z_stride) {
+  if (!z || !store) return false;
+  const int kpt = store->n_feat <= 32 ? 32 : 64;
+  return z_stride >= kpt && z_stride % 2 == 0;
+}
+
+extern "C" int64_t dr_ginet_z_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t n_feat, int32_t k0, int32_t p1_edges,
+                                        int32_t k1, int32_t transpose_aliased, int32_t out_dim, int32_t z_stride) {
+  if (z_stride < (n_feat <= 32 ? 32 : 64)) return -1;
+  return 4LL * carve(n_nodes, n_edges, n_feat, k0, p1_edges, k1, transpose_aliased, out_dim, z_stride).total;
+}
+
+extern "C" int dr_ginet_graph_pass_z(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                                     const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes, const float* z,
+                                     int32_t z_stride, void* stream) {
+  if (!z_args_ok(store, z, z_stride)) return DR_E_ARG;
+  return graph_pass_launch(store, descs, n_batch, w, pass, lds_bytes, z, z_stride, stream);
 }
 
 // Accumulating pass: n_groups workgroups, graph gi on workgroup gi % n_groups
@@ -2009,9 +2110,18 @@ extern "C" int64_t dr_ginet_acc_lds_bytes(const int32_t* max_sizes, int32_t n_fe
   return 4LL * (acc_words(n_feat, out_dim, n_feat > 32) + 4 + L.total);
 }
 
-extern "C" int dr_ginet_acc_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
-                                 const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes, int32_t n_groups,
-                                 const int32_t* plan, const int32_t* max_sizes, void* stream) {
+// dr_ginet_acc_pass (z = null) and dr_ginet_acc_pass_z.  Whether the pass can
+// run at all is decided by the gather form's sizes either way.  The Z-input
+// form's per-graph carve (lds_z_bytes: its largest graph's) is smaller than the
+// gather form's, but its prefetch layout is not always: it holds Z once per
+// parity, 2 (KPT + 4) N words against 2 (r4(F) N + N + E / 2) + (KPT + 2) N, so
+// for small F (F <= 8 at E ~ 15 N) it is the larger one.  Where the gather
+// prefetch layout fits and the Z one does not, the Z kernel without prefetch
+// runs (same results); where that does not fit either, the gather kernels.
+static int acc_pass_launch(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                           const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes, int32_t n_groups,
+                           const int32_t* plan, const int32_t* max_sizes, const float* z, int32_t z_stride,
+                           int32_t lds_z_bytes, void* stream) {
   if (!store || !descs || !w || !pass || n_batch < 0 || n_groups < 1) return DR_E_ARG;
   DR_CHECK(dr_check_loss(pass));
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
@@ -2033,6 +2143,19 @@ extern "C" int dr_ginet_acc_pass(const dr_graph_store* store, const dr_graph_des
   }
   const bool pf = lds_pf > 0 && lds_pf <= 160 * 1024;
   if (!pf && lds > 160 * 1024) return DR_E_LDS;
+  int64_t lds_z = 0, lds_pf_z = 0;
+  bool pf_z = false;
+  if (z) {
+    lds_z = (int64_t)lds_z_bytes + 4LL * (acc_words(F, OUT, F > 32) + 4);
+    if (pf) {
+      const AccLayout Lz = acc_layout(max_sizes[0], max_sizes[1], F, max_sizes[2], max_sizes[3], max_sizes[4],
+                                      store->transpose_aliased, OUT, z_stride);
+      lds_pf_z = 4LL * (acc_words(F, OUT, F > 32) + 4 + Lz.total);
+      pf_z = lds_pf_z <= 160 * 1024;
+      if (pf_z) L = Lz;
+    }
+    if (!pf_z && lds_z > 160 * 1024) z = nullptr;  // neither Z layout fits: the gather kernels, as dr_ginet_acc_pass
+  }
   if (n_batch == 0) return DR_OK;
   if (!store->cl0) return DR_E_ARG;
   if (n_groups > n_batch && !plan) n_groups = n_batch;
@@ -2042,20 +2165,74 @@ extern "C" int dr_ginet_acc_pass(const dr_graph_store* store, const dr_graph_des
   args.p = *pass;
   args.descs = descs;
   args.B = n_batch;
+  args.z = z;
+  args.z_stride = z ? z_stride : 0;
   const hipStream_t st = (hipStream_t)stream;
-#define DR_ACC_LAUNCH(KPT, PF, BYTES)                                                                   \
-  do {                                                                                                \
-    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_acc_kernel<KPT, PF>)));            \
-    hipLaunchKernelGGL((ginet_acc_kernel<KPT, PF>), dim3(n_groups), dim3(NT), (int)(BYTES), st, args, plan, L); \
+#define DR_ACC_LAUNCH(KPT, PF, ZIN, BYTES)                                                                   \
+  do {                                                                                                     \
+    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_acc_kernel<KPT, PF, ZIN>)));            \
+    hipLaunchKernelGGL((ginet_acc_kernel<KPT, PF, ZIN>), dim3(n_groups), dim3(NT), (int)(BYTES), st, args, plan, L); \
   } while (0)
-  if (F <= 32) {
-    if (pf) DR_ACC_LAUNCH(32, true, lds_pf);
-    else DR_ACC_LAUNCH(32, false, lds);
-  } else {
-    if (pf) DR_ACC_LAUNCH(64, true, lds_pf);
-    else DR_ACC_LAUNCH(64, false, lds);
-  }
+#define DR_ACC_PICK(KPT)                                 \
+  do {                                                   \
+    if (z && pf_z) DR_ACC_LAUNCH(KPT, true, true, lds_pf_z); \
+    else if (z) DR_ACC_LAUNCH(KPT, false, true, lds_z);  \
+    else if (pf) DR_ACC_LAUNCH(KPT, true, false, lds_pf); \
+    else DR_ACC_LAUNCH(KPT, false, false, lds);          \
+  } while (0)
+  if (F <= 32) DR_ACC_PICK(32);
+  else DR_ACC_PICK(64);
+#undef DR_ACC_PICK
 #undef DR_ACC_LAUNCH
+  return (int)hipGetLastError();
+}
+
+extern "C" int dr_ginet_acc_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                                 const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes, int32_t n_groups,
+                                 const int32_t* plan, const int32_t* max_sizes, void* stream) {
+  return acc_pass_launch(store, descs, n_batch, w, pass, lds_bytes, n_groups, plan, max_sizes, nullptr, 0, 0, stream);
+}
+
+extern "C" int dr_ginet_acc_pass_z(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                                   const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes, int32_t lds_z_bytes,
+                                   int32_t n_groups, const int32_t* plan, const int32_t* max_sizes, const float* z,
+                                   int32_t z_stride, void* stream) {
+  if (!z_args_ok(store, z, z_stride) || lds_z_bytes < 0) return DR_E_ARG;
+  return acc_pass_launch(store, descs, n_batch, w, pass, lds_bytes, n_groups, plan, max_sizes, z, z_stride, lds_z_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Z = A·X for whole graphs of the store (dr_aggregate_x): what conv1's gather
+// computes in every pass, once.  One workgroup per graph, one thread per
+// (row, column): the CSR row's x values added one at a time in CSR order from
+// +0.f — the chain of drk::gather_row_two_chunks*, so the same bits.  Columns
+// past F and the stride padding are written as zeros.  Not on the hot path.
+// ---------------------------------------------------------------------------
+namespace {
+__global__ void __launch_bounds__(256) aggregate_x_kernel(dr_graph_store s, float* z, int32_t z_stride, int32_t g0) {
+  const int g = g0 + blockIdx.x;
+  const int64_t n0 = s.node_off[g];
+  const int N = (int)(s.node_off[g + 1] - n0);
+  const int32_t* rp = s.rowptr + n0 + g;
+  const uint16_t* col = s.col + s.col_off[g];
+  const float* x = s.x + n0 * (int64_t)s.x_stride;
+  float* zg = z + n0 * (int64_t)z_stride;
+  for (int p = threadIdx.x; p < N * z_stride; p += blockDim.x) {
+    const int i = p / z_stride, c = p - i * z_stride;
+    float acc = 0.f;
+    if (c < s.n_feat)
+      for (int e = rp[i]; e < rp[i + 1]; ++e) acc = acc + x[(int64_t)col[e] * s.x_stride + c];
+    zg[p] = acc;
+  }
+}
+}  // namespace
+
+extern "C" int dr_aggregate_x(const dr_graph_store* store, float* z, int32_t z_stride, int32_t g0, int32_t n_graphs,
+                              void* stream) {
+  if (!store || !z || g0 < 0 || n_graphs < 0) return DR_E_ARG;
+  if (z_stride < store->n_feat || g0 + (int64_t)n_graphs > store->n_graphs) return DR_E_ARG;
+  if (n_graphs == 0) return DR_OK;
+  hipLaunchKernelGGL(aggregate_x_kernel, dim3(n_graphs), dim3(256), 0, (hipStream_t)stream, *store, z, z_stride, g0);
   return (int)hipGetLastError();
 }
 

@@ -234,6 +234,10 @@ SIGNATURES = [
     ("dr_ginet_acc_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, ctypes.c_int32, VP, _c_i32, VP]),
     ("dr_ginet_acc_row_floats", ctypes.c_int32, [ctypes.c_int32] * 2),
     ("dr_ginet_acc_lds_bytes", ctypes.c_int64, [_c_i32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    ("dr_aggregate_x", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, VP]),
+    ("dr_ginet_graph_pass_z", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, VP, ctypes.c_int32, VP]),
+    ("dr_ginet_acc_pass_z", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, VP, _c_i32, VP, ctypes.c_int32, VP]),
+    ("dr_ginet_z_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 9),
     ("dr_ginet_large_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(LargePlanC), ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, ctypes.c_int32, VP]),
     ("dr_ginet_large_conv_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 5),
     ("dr_ginet_nocluster_large_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(NcPlanC), ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), VP]),

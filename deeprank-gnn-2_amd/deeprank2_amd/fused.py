@@ -414,6 +414,23 @@ def lds_for(spec: FusedSpec, h: BatchHandle, out_dim):
     return h.lds((spec.entry, out_dim), lambda n, e, k0, p1, k1: spec.lds(n, e, k0, p1, k1, f, alias, out_dim))
 
 
+def agg_x_for(spec: FusedSpec, h: BatchHandle):
+    """The store's Z = A x array (``GraphStore.agg_x``) when this batch's fp32
+    per-graph or accumulating GINet pass can read it instead of gathering
+    (``dr_ginet_graph_pass_z`` / ``dr_ginet_acc_pass_z``), else None: another
+    model, a batch with non-finite inputs, the switch off, or the array still
+    missing while the stream is capturing."""
+    if spec.entry != "dr_ginet_graph_pass" or h.nonfinite:
+        return None
+    return h.store.agg_x()
+
+
+def z_lds_for(h: BatchHandle, out_dim):
+    """Dynamic LDS bytes of the Z-input kernels for the batch's largest graph."""
+    alias, f, zs = int(h.store.packed.transpose_aliased), h.store.n_feat, h.store.agg_x_stride
+    return h.lds(("dr_ginet_z_lds_bytes", out_dim, zs), lambda n, e, k0, p1, k1: _lib.load().dr_ginet_z_lds_bytes(n, e, f, k0, p1, k1, alias, out_dim, zs))
+
+
 def launch(spec: FusedSpec, h: BatchHandle, w, p, wpack=None):
     """One graph pass on the current stream: the single-workgroup kernel when
     the batch's largest graph fits in LDS, else the model's large-graph path.
@@ -435,6 +452,11 @@ def launch(spec: FusedSpec, h: BatchHandle, w, p, wpack=None):
         return
     lds = lds_for(spec, h, p.out_dim)
     if lds <= LDS_MAX and not (h.force_large and spec.large is not None):
+        z = agg_x_for(spec, h)
+        if z is not None:  # (the path was chosen by the gather form's LDS above; the per-graph Z carve drops x, rowptr and col for 2 N words and is always smaller)
+            rc = _lib.load().dr_ginet_graph_pass_z(h.store.cstruct(), h.descs.data_ptr(), h.B, w, p, z_lds_for(h, p.out_dim), z.data_ptr(), h.store.agg_x_stride, _lib.stream_ptr(h.store.device))
+            _lib.check(rc, "dr_ginet_graph_pass_z")
+            return
         fn = getattr(_lib.load(), spec.entry)
         _lib.check(fn(h.store.cstruct(), h.descs.data_ptr(), h.B, w, p, lds, _lib.stream_ptr(h.store.device)), spec.entry)
     elif spec.large is not None:

@@ -24,6 +24,7 @@ Per graph the index arrays use local int32 ids; offsets are int64.
 
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -381,6 +382,11 @@ class GraphStore:
         self.edge_attr = None if p.edge_attr is None else t(p.edge_attr)
         self._sizes = p.sizes()
         self._c = None
+        # Z = A x (agg_x), built on first need.  Like x_bf16 it is derived from
+        # x (and the CSR): both assume x is never written after construction.
+        self._agg_x = None
+        # False: GINet's passes gather in the kernel (DR_GINET_AGGX=0 in the environment, read here once)
+        self.use_agg_x = os.environ.get("DR_GINET_AGGX", "1") != "0"
 
     @property
     def n_graphs(self):
@@ -414,6 +420,49 @@ class GraphStore:
                 s.x_bf16_stride = self.x_bf16_stride
             self._c = s
         return self._c
+
+    # Row stride of agg_x beyond the kernels' K (32 for F <= 32, else 64): the
+    # stride in HBM is the LDS row stride of the kernels that DMA the blocks in.
+    # AGG_X_PAD is set in DESIGN §5's A/B: 4 gives 16-byte rows (16-byte DMA lanes,
+    # 2-way bank conflicts on the MFMA operand reads), 2 is conflict-free with
+    # 4-byte lanes.
+    AGG_X_PAD = 4
+
+    @property
+    def agg_x_stride(self):
+        return (32 if self.n_feat <= 32 else 64) + self.AGG_X_PAD  # noqa: PLR2004
+
+    def agg_x(self):
+        """Conv1's neighbour sums Z = A x of every graph, ``[N_all, agg_x_stride]``
+        fp32 (``dr_aggregate_x``: bit for bit what GINet's kernels gather, zeros
+        past F), or None.  Built on first need by one launch over the whole
+        store and kept: it doubles the store's feature memory (N_all x stride
+        floats, +28.8 KB per 200-residue graph at the 36-word stride) and
+        assumes, like ``x_bf16``, that ``x`` is never written after
+        construction.  None when switched off (``use_agg_x = False``; the
+        constructor sets that for ``DR_GINET_AGGX=0``), and when it is still
+        missing while the stream is capturing (nothing is allocated or built
+        under capture: the caller takes the gather entry)."""
+        if not self.use_agg_x:
+            return None
+        if self._agg_x is None:
+            self._agg_x = self._build_agg_x()
+        return self._agg_x
+
+    def _build_agg_x(self):
+        import torch  # noqa: PLC0415
+
+        from deeprank2_amd import _lib  # noqa: PLC0415
+
+        if self.device.type != "cuda" or torch.cuda.is_current_stream_capturing():
+            return None
+        stride = self.agg_x_stride
+        with torch.cuda.device(self.device):
+            z = torch.empty((max(1, int(self.x.shape[0])), stride), dtype=torch.float32, device=self.device)
+            rc = _lib.load().dr_aggregate_x(self.cstruct(), z.data_ptr(), stride, 0, self.n_graphs, _lib.stream_ptr(self.device))
+            _lib.check(rc, "dr_aggregate_x")
+            torch.cuda.current_stream(self.device).synchronize()  # later passes may run on other streams
+        return z
 
     def descriptors(self, gids_host):
         """dr_graph_desc records (64 bytes each) for these graph ids, as a device uint8 tensor."""

@@ -261,6 +261,46 @@ int32_t dr_ginet_acc_row_floats(int32_t n_feat, int32_t out_dim);
  * maxima (host int32 [5] as above), or -1 for NULL.                          */
 int64_t dr_ginet_acc_lds_bytes(const int32_t* max_sizes, int32_t n_feat, int32_t transpose_aliased, int32_t out_dim);
 
+/* ---- conv1's neighbour sums, once per store instead of once per pass ----
+ * conv1 aggregates first (attention == 1): H = relu((A X) [W1;W1e]^T), and its
+ * weight gradient is sum_k v_k Z[arg_k] with Z = A X, so Z depends only on the
+ * store's x and CSR.  dr_aggregate_x writes Z for graphs g0 .. g0 + n_graphs - 1:
+ * node i of the store at z + i * z_stride (z: device, [N_all, z_stride] fp32,
+ * z_stride >= F).  Row i of a graph is the sum of x[col[e]] over its CSR row in
+ * CSR order, one fp32 add at a time from +0 -- bit for bit what the passes'
+ * own gather computes; columns F .. z_stride - 1 are written as zeros.  The
+ * array is valid as long as x, rowptr and col are unchanged.                  */
+int dr_aggregate_x(const dr_graph_store* store, float* z, int32_t z_stride, int32_t g0, int32_t n_graphs,
+                   void* stream);
+
+/* dr_ginet_graph_pass / dr_ginet_acc_pass reading that array instead of
+ * gathering: each workgroup DMAs its graph's Z block straight into LDS in the
+ * place of x, col and rowptr.  Same results, bit for bit.  z_stride is the LDS
+ * row stride too: even, and at least the kernel's K (32 for F <= 32, else
+ * 64), else DR_E_ARG; a multiple of 4 lets the copy run in 16-byte lanes.
+ * lds_bytes of dr_ginet_graph_pass_z: dr_ginet_z_lds_bytes of the batch's
+ * largest graph.  dr_ginet_acc_pass_z: lds_bytes and max_sizes as for
+ * dr_ginet_acc_pass (whether the pass can run is decided exactly as there),
+ * lds_z_bytes = dr_ginet_z_lds_bytes of the batch maxima.  The Z form's
+ * prefetch layout keeps Z once per parity and is larger than the gather
+ * form's for small F (F <= 8 at E ~ 15 N): where the gather prefetch layout
+ * fits 160 KB and the Z one does not, the Z kernel runs without prefetch, and
+ * where that does not fit either, the gather kernels of dr_ginet_acc_pass --
+ * never DR_E_LDS for a batch dr_ginet_acc_pass accepts.  Same results.       */
+int dr_ginet_graph_pass_z(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                          const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes,
+                          const float* z, int32_t z_stride, void* stream);
+int dr_ginet_acc_pass_z(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                        const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes, int32_t lds_z_bytes,
+                        int32_t n_groups, const int32_t* plan, const int32_t* max_sizes,
+                        const float* z, int32_t z_stride, void* stream);
+/* Dynamic LDS bytes of dr_ginet_graph_pass_z for a graph of these sizes
+ * (smaller than dr_ginet_lds_bytes: no x, col, rowptr), or -1 for a z_stride
+ * below the kernel's K.                                                      */
+int64_t dr_ginet_z_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t n_feat, int32_t k0,
+                             int32_t p1_edges, int32_t k1, int32_t transpose_aliased, int32_t out_dim,
+                             int32_t z_stride);
+
 /* ---- GINet on graphs larger than one workgroup's LDS (atom-level graphs) ----
  * Two launches with the same result as dr_ginet_graph_pass:
  *   1. one workgroup per tile of plan->tile_rows nodes: Z = A X for its rows
