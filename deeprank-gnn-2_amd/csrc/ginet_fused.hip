@@ -1235,6 +1235,53 @@ __global__ void __launch_bounds__(NT) ginet_graph_kernel(GinetArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// Several members in one launch (dr_ginet_multi_pass): a batch of 64 graphs
+// occupies 64 of the 256 CUs for the length of one graph's chain of phases, so
+// up to DR_MAX_MEMBERS independent models (an ensemble, the folds of a
+// cross-validation, a sweep) run side by side on a grid (max B_k, K).  Row
+// blockIdx.y is member y: its weights, its whole dr_pass and its batch; the
+// store and Z are shared.  The body is graph_body as ginet_graph_kernel calls
+// it (the graph from blockIdx.x, everything else from GinetArgs), so a member
+// computes what its own launch computes.
+// ---------------------------------------------------------------------------
+struct MultiMemberArgs {
+  dr_ginet_weights w;
+  dr_pass p;
+  const dr_graph_desc* descs;
+  int32_t B, pad;
+};
+struct MultiArgs {
+  dr_graph_store s;
+  const float* z;
+  int32_t z_stride, n_members;
+  MultiMemberArgs m[DR_MAX_MEMBERS];
+};
+// the kernel-argument segment: 4 KB, of which the runtime's hidden arguments take up to 256 bytes
+static_assert(sizeof(MultiArgs) <= 4096 - 256, "DR_MAX_MEMBERS members by value must fit the kernel arguments");
+
+template <int KPT, bool ZIN>
+__global__ void __launch_bounds__(NT) ginet_multi_kernel(MultiArgs ma) {
+  // the member's record is read with scalar loads through a kernarg pointer
+  // the optimiser cannot follow (as ginet_acc_kernel's): indexing the by-value
+  // array with blockIdx.y would put it in scratch or in spilled SGPRs
+  typedef const __attribute__((address_space(4))) MultiArgs* KArgs;
+  KArgs kp = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("; dr_kargs" : "+s"(kp));
+  const MultiArgs* ka = (const MultiArgs*)kp;
+  const int k = blockIdx.y;
+  if ((int)blockIdx.x >= ka->m[k].B) return;  // past this member's batch (before the first barrier)
+  GinetArgs a;
+  a.s = ka->s;
+  a.w = ka->m[k].w;
+  a.p = ka->m[k].p;
+  a.descs = ka->m[k].descs;
+  a.B = ka->m[k].B;
+  a.z = ka->z;
+  a.z_stride = ka->z_stride;
+  graph_body<KPT, false, false, ZIN>(a, AccCtx{});
+}
+
+// ---------------------------------------------------------------------------
 // Accumulating pass (dr_ginet_acc_pass; batches past the CU count): R
 // workgroups, workgroup w runs graphs w, w + R, w + 2R, ... in that order and
 // sums their gradients on chip — the conv weights' and the head's in an LDS
@@ -2028,10 +2075,10 @@ extern "C" int64_t dr_ginet_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t 
   return 4LL * carve(n_nodes, n_edges, n_feat, k0, p1_edges, k1, transpose_aliased, out_dim).total;
 }
 
-// dr_ginet_graph_pass (z = null) and dr_ginet_graph_pass_z
-static int graph_pass_launch(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
-                             const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes, const float* z,
-                             int32_t z_stride, void* stream) {
+// What dr_ginet_graph_pass, dr_ginet_graph_pass_z and (per member)
+// dr_ginet_multi_pass check before anything is launched
+static int graph_pass_check(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                            const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes) {
   if (!store || !descs || !w || !pass || n_batch < 0) return DR_E_ARG;
   DR_CHECK(dr_check_loss(pass));
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
@@ -2043,6 +2090,14 @@ static int graph_pass_launch(const dr_graph_store* store, const dr_graph_desc* d
   if ((pass->flags & DR_PASS_FORWARD) && !pass->out) return DR_E_ARG;
   if (pass->use_dropout == DR_DROPOUT_MASK && !pass->mask) return DR_E_ARG;
   if (pass->use_dropout < DR_DROPOUT_OFF || pass->use_dropout > DR_DROPOUT_HASH) return DR_E_ARG;
+  return DR_OK;
+}
+
+// dr_ginet_graph_pass (z = null) and dr_ginet_graph_pass_z
+static int graph_pass_launch(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                             const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes, const float* z,
+                             int32_t z_stride, void* stream) {
+  DR_CHECK(graph_pass_check(store, descs, n_batch, w, pass, lds_bytes));
   if (n_batch == 0) return DR_OK;
   if (!store->cl0) return DR_E_ARG;
   GinetArgs args;
@@ -2093,6 +2148,49 @@ extern "C" int dr_ginet_graph_pass_z(const dr_graph_store* store, const dr_graph
                                      int32_t z_stride, void* stream) {
   if (!z_args_ok(store, z, z_stride)) return DR_E_ARG;
   return graph_pass_launch(store, descs, n_batch, w, pass, lds_bytes, z, z_stride, stream);
+}
+
+extern "C" int dr_ginet_multi_pass(const dr_graph_store* store, const dr_ginet_member* members, int32_t n_members,
+                                   int32_t lds_bytes, const float* z, int32_t z_stride, void* stream) {
+  if (!store || !members || n_members < 1 || n_members > DR_MAX_MEMBERS) return DR_E_ARG;
+  if (z && !z_args_ok(store, z, z_stride)) return DR_E_ARG;
+  int max_b = 0;
+  for (int k = 0; k < n_members; ++k) {
+    const dr_ginet_member& m = members[k];
+    DR_CHECK(graph_pass_check(store, m.descs, m.n_batch, m.w, m.pass, lds_bytes));
+    if (m.pass->slot) return DR_E_UNSUPPORTED;  // (a batch split over launches runs the members' own passes)
+    if (m.pass->out_dim != members[0].pass->out_dim) return DR_E_UNSUPPORTED;
+    max_b = m.n_batch > max_b ? m.n_batch : max_b;
+  }
+  if (max_b == 0) return DR_OK;
+  if (!store->cl0) return DR_E_ARG;
+  MultiArgs args;
+  std::memset(&args, 0, sizeof(args));
+  args.s = *store;
+  args.z = z;
+  args.z_stride = z ? z_stride : 0;
+  args.n_members = n_members;
+  for (int k = 0; k < n_members; ++k) {
+    args.m[k].w = *members[k].w;
+    args.m[k].p = *members[k].pass;
+    args.m[k].descs = members[k].descs;
+    args.m[k].B = members[k].n_batch;
+  }
+#define DR_MULTI_LAUNCH(KPT, ZIN)                                                                                  \
+  do {                                                                                                             \
+    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_multi_kernel<KPT, ZIN>)));                      \
+    hipLaunchKernelGGL((ginet_multi_kernel<KPT, ZIN>), dim3(max_b, n_members), dim3(NT), lds_bytes,                \
+                       (hipStream_t)stream, args);                                                                 \
+  } while (0)
+  if (store->n_feat <= 32) {
+    if (z) DR_MULTI_LAUNCH(32, true);
+    else DR_MULTI_LAUNCH(32, false);
+  } else {
+    if (z) DR_MULTI_LAUNCH(64, true);
+    else DR_MULTI_LAUNCH(64, false);
+  }
+#undef DR_MULTI_LAUNCH
+  return (int)hipGetLastError();
 }
 
 // Accumulating pass: n_groups workgroups, graph gi on workgroup gi % n_groups

@@ -1,6 +1,7 @@
 // Gradient reduction over the batch + the optimizer update, the second launch
 // of every fused model's training step (dr_reduce_update: torch.optim.Adam;
-// dr_reduce_update_opt: Adam, AdamW or Adamax by dr_optim.kind).
+// dr_reduce_update_opt: Adam, AdamW or Adamax by dr_optim.kind;
+// dr_reduce_update_multi: the same for up to DR_MAX_MEMBERS models at once).
 //
 // Replaces loss_.backward()'s accumulation over the batch and
 // optimizer.step() of Trainer._epoch (deeprank2/trainer.py:689-690) for the
@@ -391,7 +392,106 @@ int reduce_launch(int kind, const dr_param_table* t, const float* slab, const fl
   return (int)hipGetLastError();
 }
 
+// ---- several members in one launch (dr_reduce_update_multi) ---------------
+// The argument buffer, in device memory: the block map the members share, then
+// one header + record array per member.  (K ReduceArgs are ~3.3 KB each: past
+// the kernel-argument segment.)
+struct alignas(64) MultiHead {
+  int32_t n_members, n_blocks, kind, pad[13];
+  uint8_t blk_param[DR_REDUCE_MAX_BLOCKS];
+  uint16_t blk_elem[DR_REDUCE_MAX_BLOCKS];
+};
+struct alignas(64) MultiMember {
+  ReduceHdr h;
+  ParamRec rec[DR_MAX_PARAMS];
+};
+static_assert(sizeof(MultiHead) % 64 == 0 && sizeof(MultiMember) % 64 == 0, "members start on 64-byte lines");
+
+// Grid (n_blocks, K): block (j, k) is block j of member k's reduce_kernel<OPT>.
+// The buffer is read-only for the launch: its map, header and record are read
+// through the constant address space (scalar loads, as the kernel arguments
+// of reduce_kernel are).
+template <int OPT>
+__global__ void __launch_bounds__(RT) reduce_multi_kernel(const void* args) {
+  __shared__ float part[RC][RP];
+  typedef const __attribute__((address_space(4))) MultiHead* CHead;
+  typedef const __attribute__((address_space(4))) MultiMember* CMember;
+  const CHead hd = (CHead)args;
+  const int j = blockIdx.x, k = blockIdx.y;
+  if (j >= hd->n_blocks || k >= hd->n_members) return;
+  const CMember m = (CMember)((const __attribute__((address_space(4))) char*)args + sizeof(MultiHead)) + k;
+  if (m->h.B == 0) return;  // the member sits this step out
+  const int pi = hd->blk_param[j];
+  const int eb = hd->blk_elem[j];
+  const ReduceHdr& h = *(const ReduceHdr*)&m->h;
+  const ParamRec& r = *(const ParamRec*)&m->rec[pi];
+  // (every line of the header and the record the block uses, in one scalar round trip: as reduce_kernel)
+  asm volatile("" ::"s"(h.slab), "s"(h.head), "s"(h.B), "s"(h.slab_stride), "s"(h.head_stride), "s"(h.adam_enabled),
+               "s"(r.param), "s"(r.grad), "s"(r.m), "s"(r.v), "s"(r.numel), "s"(r.kind), "s"(r.off1), "s"(r.off2), "s"(r.cols));
+  const int64_t tstep = (h.step_counter && h.adam_enabled) ? h.step_counter[1] + 1 : 0;
+  reduce_block<OPT>(h, r, eb, j == 0, threadIdx.x, part, tstep);
+}
+
 }  // namespace
+
+extern "C" int64_t dr_reduce_multi_args_bytes(int32_t n_members) {
+  if (n_members < 1 || n_members > DR_MAX_MEMBERS) return -1;
+  return (int64_t)sizeof(MultiHead) + (int64_t)n_members * (int64_t)sizeof(MultiMember);
+}
+
+extern "C" int dr_reduce_multi_build(const dr_reduce_member* members, int32_t n_members, void* host_buf, int64_t bytes) {
+  if (!members || !host_buf || n_members < 1 || n_members > DR_MAX_MEMBERS) return DR_E_ARG;
+  if (bytes < dr_reduce_multi_args_bytes(n_members)) return DR_E_ARG;
+  // (built aside, so host_buf needs no alignment; it is left untouched on an error)
+  MultiHead hd;
+  std::memset(&hd, 0, sizeof(hd));
+  MultiMember mm[DR_MAX_MEMBERS];
+  const dr_param_table* t0 = members[0].t;
+  const int kind = members[0].opt.kind;
+  if (kind != DR_OPT_ADAM && kind != DR_OPT_ADAMW && kind != DR_OPT_ADAMAX) return DR_E_ARG;
+  int blocks = 0;
+  for (int k = 0; k < n_members; ++k) {
+    const dr_reduce_member& m = members[k];
+    if (m.opt.kind != kind) return DR_E_ARG;
+    std::memset(&mm[k], 0, sizeof(MultiMember));
+    const int b = build_reduce(m.t, m.slab, m.head, m.n_batch, &m.opt.adam, m.loss_per_graph, m.loss_scale, m.loss_out,
+                               mm[k].h, mm[k].rec);
+    if (b < 0) return b;
+    if (b > DR_REDUCE_MAX_BLOCKS) return DR_E_UNSUPPORTED;
+    // one block map: the members' parameters have the same sizes
+    if (m.t->n_params != t0->n_params) return DR_E_ARG;
+    for (int i = 0; i < t0->n_params; ++i)
+      if (m.t->numel[i] != t0->numel[i]) return DR_E_ARG;
+    mm[k].h.om_beta1 = m.opt.om_beta1 != 0.f ? m.opt.om_beta1 : 1.f - m.opt.adam.beta1;
+    mm[k].h.om_beta2 = m.opt.om_beta2 != 0.f ? m.opt.om_beta2 : 1.f - m.opt.adam.beta2;
+    blocks = b;
+  }
+  int j = 0;
+  for (int i = 0; i < t0->n_params; ++i)
+    for (int x = 0; x * RP < t0->numel[i]; ++x, ++j) {
+      hd.blk_param[j] = (uint8_t)i;
+      hd.blk_elem[j] = (uint16_t)x;
+    }
+  hd.n_members = n_members;
+  hd.n_blocks = blocks;
+  hd.kind = kind;
+  std::memcpy(host_buf, &hd, sizeof(hd));
+  std::memcpy(static_cast<char*>(host_buf) + sizeof(hd), mm, (size_t)n_members * sizeof(MultiMember));
+  return blocks;
+}
+
+extern "C" int dr_reduce_update_multi(const void* dev_args, int32_t n_members, int32_t n_blocks, int32_t opt_kind,
+                                      void* stream) {
+  if (!dev_args || (reinterpret_cast<uintptr_t>(dev_args) & 63)) return DR_E_ARG;
+  if (n_members < 1 || n_members > DR_MAX_MEMBERS || n_blocks < 0 || n_blocks > DR_REDUCE_MAX_BLOCKS) return DR_E_ARG;
+  if (opt_kind != DR_OPT_ADAM && opt_kind != DR_OPT_ADAMW && opt_kind != DR_OPT_ADAMAX) return DR_E_ARG;
+  if (n_blocks == 0) return DR_OK;
+  auto kernel = opt_kind == DR_OPT_ADAMW    ? reduce_multi_kernel<DR_OPT_ADAMW>
+                : opt_kind == DR_OPT_ADAMAX ? reduce_multi_kernel<DR_OPT_ADAMAX>
+                                            : reduce_multi_kernel<DR_OPT_ADAM>;
+  hipLaunchKernelGGL(kernel, dim3(n_blocks, n_members), dim3(RT), 0, (hipStream_t)stream, dev_args);
+  return (int)hipGetLastError();
+}
 
 extern "C" int dr_reduce_update(const dr_param_table* t, const float* slab, const float* head, int32_t n_batch,
                                 const dr_adam* adam, const float* loss_per_graph, float loss_scale, float* loss_out,

@@ -227,6 +227,22 @@ class ParamTableC(ctypes.Structure):
     ]
 
 
+DR_MAX_MEMBERS = 8
+
+
+class GinetMemberC(ctypes.Structure):
+    """dr_ginet_member: one model of dr_ginet_multi_pass (host pointers to its structs)."""
+
+    _fields_ = [("w", ctypes.POINTER(GinetWeightsC)), ("pass_", ctypes.POINTER(PassC)), ("descs", VP), ("n_batch", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class ReduceMemberC(ctypes.Structure):
+    """dr_reduce_member: what dr_reduce_update_opt takes, for one model of dr_reduce_multi_build."""
+
+    _fields_ = [("t", ctypes.POINTER(ParamTableC)), ("slab", VP), ("head", VP), ("loss_per_graph", VP), ("loss_out", VP),
+                ("n_batch", ctypes.c_int32), ("loss_scale", ctypes.c_float), ("opt", OptimC)]  # fmt: skip
+
+
 # (name, restype, argtypes) for every entry of include/deeprank2_amd.h
 SIGNATURES = [
     ("dr_ginet_graph_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, VP]),
@@ -238,6 +254,10 @@ SIGNATURES = [
     ("dr_ginet_graph_pass_z", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, VP, ctypes.c_int32, VP]),
     ("dr_ginet_acc_pass_z", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, VP, _c_i32, VP, ctypes.c_int32, VP]),
     ("dr_ginet_z_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 9),
+    ("dr_ginet_multi_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), ctypes.POINTER(GinetMemberC), ctypes.c_int32, ctypes.c_int32, VP, ctypes.c_int32, VP]),
+    ("dr_reduce_multi_args_bytes", ctypes.c_int64, [ctypes.c_int32]),
+    ("dr_reduce_multi_build", ctypes.c_int, [ctypes.POINTER(ReduceMemberC), ctypes.c_int32, VP, ctypes.c_int64]),
+    ("dr_reduce_update_multi", ctypes.c_int, [VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, VP]),
     ("dr_ginet_large_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(LargePlanC), ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, ctypes.c_int32, VP]),
     ("dr_ginet_large_conv_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 5),
     ("dr_ginet_nocluster_large_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(NcPlanC), ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), VP]),

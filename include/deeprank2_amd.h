@@ -301,6 +301,34 @@ int64_t dr_ginet_z_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t n_feat, i
                              int32_t p1_edges, int32_t k1, int32_t transpose_aliased, int32_t out_dim,
                              int32_t z_stride);
 
+/* Up to DR_MAX_MEMBERS independent GINet models (an ensemble, the folds of a
+ * cross-validation, a hyper-parameter sweep) over ONE store in ONE launch:
+ * a 2-D grid (max_k n_batch_k, n_members) whose row k runs member k's
+ * per-graph pass (dr_ginet_graph_pass, or with z != NULL dr_ginet_graph_pass_z)
+ * -- the same code on the same arguments, so every member's out, slab, head,
+ * loss_per_graph and step-counter snapshot hold the bits that member's own
+ * launch would write.  Each member brings its weights, its whole dr_pass (its
+ * buffers, step counter, dropout seed, loss, loss_scale, class_w) and its batch
+ * (descs, n_batch); the store, z and z_stride are shared.  members is a host
+ * array of host pointers.  A workgroup past its member's batch returns at
+ * once: a member with n_batch == 0 touches nothing and its step counter is not
+ * snapshotted.  lds_bytes: the largest carve any member's batch needs
+ * (dr_ginet_lds_bytes, or dr_ginet_z_lds_bytes with z).  Every member passes
+ * the checks of dr_ginet_graph_pass; DR_E_ARG for n_members outside
+ * 1..DR_MAX_MEMBERS or a NULL member field, DR_E_UNSUPPORTED for bf16, a slot
+ * array, or members whose out_dim differ.  DR_OK without a launch when every
+ * n_batch is 0.                                                              */
+#define DR_MAX_MEMBERS 8
+typedef struct dr_ginet_member {
+  const dr_ginet_weights* w;
+  const dr_pass* pass;
+  const dr_graph_desc* descs; /* device [n_batch] */
+  int32_t n_batch;
+  int32_t pad;
+} dr_ginet_member;
+int dr_ginet_multi_pass(const dr_graph_store* store, const dr_ginet_member* members, int32_t n_members,
+                        int32_t lds_bytes, const float* z, int32_t z_stride, void* stream);
+
 /* ---- GINet on graphs larger than one workgroup's LDS (atom-level graphs) ----
  * Two launches with the same result as dr_ginet_graph_pass:
  *   1. one workgroup per tile of plan->tile_rows nodes: Z = A X for its rows
@@ -715,6 +743,40 @@ typedef struct dr_optim {
 int dr_reduce_update_opt(const dr_param_table* t, const float* slab, const float* head, int32_t n_batch,
                          const dr_optim* opt, const float* loss_per_graph, float loss_scale, float* loss_out,
                          void* stream);
+
+/* dr_reduce_update_opt for the members of dr_ginet_multi_pass in ONE launch:
+ * a grid (n_blocks, n_members) whose row k runs member k's reduce + update --
+ * the same code in the same order, so the same bits.  The members share the
+ * architecture (equal numel and recipes, hence one block map) and the update
+ * rule's kind; lr, weight_decay, betas, eps, n_batch, loss_scale and every
+ * pointer are per member.  The per-member argument blocks are too large to
+ * travel by value, so they live in device memory:
+ *   dr_reduce_multi_args_bytes  size of the argument buffer for n_members
+ *                               (-1 outside 1..DR_MAX_MEMBERS);
+ *   dr_reduce_multi_build       host only: checks every member as
+ *                               dr_reduce_update_opt does and fills host_buf
+ *                               (bytes >= the size above); returns the block
+ *                               count n_blocks, or a negative DR_E_* code;
+ *   dr_reduce_update_multi      the launch; dev_args is a device copy of those
+ *                               bytes (64-byte aligned), made by the caller
+ *                               beforehand and read-only for the launch.  No
+ *                               allocation, copy or sync: capturable.
+ * A member with n_batch == 0 sits the step out: its row of blocks returns at
+ * once (no update, no counter advance, no loss write).                        */
+typedef struct dr_reduce_member {
+  const dr_param_table* t;
+  const float* slab;
+  const float* head;
+  const float* loss_per_graph;
+  float* loss_out;
+  int32_t n_batch;
+  float loss_scale;
+  dr_optim opt;
+} dr_reduce_member;
+int64_t dr_reduce_multi_args_bytes(int32_t n_members);
+int dr_reduce_multi_build(const dr_reduce_member* members, int32_t n_members, void* host_buf, int64_t bytes);
+int dr_reduce_update_multi(const void* dev_args, int32_t n_members, int32_t n_blocks, int32_t opt_kind,
+                           void* stream);
 
 /* ---- generic layer kernels (arbitrary edge lists; GINetConvLayer API) ---- */
 
