@@ -57,6 +57,9 @@ namespace {
 #ifndef DR_ZIN_EARLY_W
 #define DR_ZIN_EARLY_W 1  // Z-input kernels: conv2 / head weights requested with the staging DMA (0: after the staging barrier, as the gather kernels; A/B)
 #endif
+#ifndef DR_W1_IMAGE
+#define DR_W1_IMAGE 1  // KPT = 32: conv1's B operands staged as a lane-ordered image and read 16 bytes at a time (0: row-major [W1; W1e], 4-byte reads; A/B)
+#endif
 #ifndef DR_DMA_ROT
 #define DR_DMA_ROT 0  // 1: spread starting waves (measured 0.1 us slower per pass, r05)
 #endif
@@ -330,6 +333,90 @@ __device__ __forceinline__ void dma_x4_async(void* lds_dst, const void* gsrc, in
 
 __device__ __forceinline__ float4 f4add(float4 a, float4 v) {
   return make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
+}
+
+// ---- the head's fc1.weight [128, 64] in the two register layouts ginet_head reads ----
+//   row layout:    thread t holds W[t >> 3][8 * (t & 7) .. + 7]   (wave w: rows 8w .. 8w + 7, whole)
+//   column layout: thread t holds W[8 * (t >> 6) + j][t & 63], j = 0 .. 7
+// and the bias of row t >> 3.  (Wave w's two layouts are the same 8 x 64 tile,
+// fetched twice.  Fetching it once and transposing it in LDS was measured and
+// not kept: DESIGN.md §5, "weights once".)
+__device__ __forceinline__ void fc1_load(const dr_ginet_weights& w, int tid, int wave, float (&row)[8], float (&col)[8],
+                                         float& bias) {
+  const int r = tid >> 3, part = tid & 7;
+  const float4 u0 = *reinterpret_cast<const float4*>(w.fc1w + r * 64 + part * 8);
+  const float4 u1 = *reinterpret_cast<const float4*>(w.fc1w + r * 64 + part * 8 + 4);
+  row[0] = u0.x; row[1] = u0.y; row[2] = u0.z; row[3] = u0.w;
+  row[4] = u1.x; row[5] = u1.y; row[6] = u1.z; row[7] = u1.w;
+  bias = w.fc1b[r];
+  const int o = tid & 63;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) col[j] = w.fc1w[(wave * 8 + j) * 64 + o];
+}
+
+// ---- conv1's B operands of v_mfma_f32_16x16x4_f32, KPT = 32 ----
+// Lane (li, kq) = (lane & 15, lane >> 4) holds, in register r of its 16 (wa[r]
+// for r < 8: conv1, row li of W1; wb[r - 8]: conv1_ext, row li of W1e), the
+// element at k = 16 * ((r & 7) >> 2) + 4 * (r & 3) + kq, zero past F.  The
+// image is those 1 024 words in the order the lanes read them: four planes of
+// 64 lanes x 4 words, lane l's registers 4p .. 4p + 3 at plane p, words 4l ..
+// 4l + 3 — one 16-byte read per plane, consecutive lanes on consecutive 16-byte
+// slots (conflict-free).  w1_image_src: image word -> its element of the packed
+// [W1; W1e] (32 rows of F), or -1: zero.  The staging DMA (per-lane source
+// address, linear LDS destination), the reads and the host test share it.
+__host__ __device__ inline int w1_image_word(int lane, int r) { return (r >> 2) * 256 + lane * 4 + (r & 3); }
+__host__ __device__ inline int w1_image_src(int F, int word) {
+  const int p = word >> 8, l = (word >> 2) & 63, q = word & 3;
+  const int li = l & 15, kq = l >> 4;
+  const int kk = 16 * (p & 1) + 4 * q + kq;
+  return kk < F ? ((p >> 1) * 16 + li) * F + kk : -1;
+}
+
+// Stage conv1's weights: the image (IMG; NT threads, one word each: one DMA
+// instruction per wave, lanes of zero words masked off) or the packed rows.
+template <bool IMG>
+__device__ __forceinline__ void w1_stage(float* sW1, float* img, const dr_ginet_weights& w, int F, int tid) {
+  if (IMG) {
+    static_assert(NT == 1024, "one image word per thread");
+    const int src = w1_image_src(F, tid);
+    const int base = __builtin_amdgcn_readfirstlane(tid & ~63);
+    if (src >= 0) {
+      const float* g = tid < 512 ? w.w1 + src : w.w1e + (src - 16 * F);  // (planes 0, 1: W1; 2, 3: W1e)
+      __builtin_amdgcn_global_load_lds(AS1(g), AS3(img + base), 4, 0, 0);
+    }
+  } else {
+    dma_words(sW1, w.w1, 16 * F, tid, DR_DMA_ROT * 5);  // [W1; W1e] rows of F, packed
+    dma_words(sW1 + 16 * F, w.w1e, 16 * F, tid, DR_DMA_ROT * 14);
+  }
+}
+// the image's zero words (k >= F), by plain stores beside the DMA
+template <bool IMG>
+__device__ __forceinline__ void w1_zero_pad(float* img, int F, int tid) {
+  if (IMG && w1_image_src(F, tid) < 0) img[tid] = 0.f;
+}
+// after the staging barrier: the lane's operands
+template <int KPT, bool IMG>
+__device__ __forceinline__ void w1_operands(const float* sW1, const float* img, int F, int lane, float (&wa)[KPT / 4],
+                                            float (&wb)[KPT / 4]) {
+  if constexpr (IMG) {
+    static_assert(KPT == 32, "the image holds 8 + 8 registers per lane");
+    const float4 a0 = *reinterpret_cast<const float4*>(img + w1_image_word(lane, 0));
+    const float4 a1 = *reinterpret_cast<const float4*>(img + w1_image_word(lane, 4));
+    const float4 b0 = *reinterpret_cast<const float4*>(img + w1_image_word(lane, 8));
+    const float4 b1 = *reinterpret_cast<const float4*>(img + w1_image_word(lane, 12));
+    wa[0] = a0.x; wa[1] = a0.y; wa[2] = a0.z; wa[3] = a0.w;
+    wa[4] = a1.x; wa[5] = a1.y; wa[6] = a1.z; wa[7] = a1.w;
+    wb[0] = b0.x; wb[1] = b0.y; wb[2] = b0.z; wb[3] = b0.w;
+    wb[4] = b1.x; wb[5] = b1.y; wb[6] = b1.z; wb[7] = b1.w;
+  } else {
+    const int li = lane & 15, kq = lane >> 4;
+#pragma unroll
+    for (int j = 0; j < KPT / 4; ++j) {
+      const int kk = 16 * (j >> 2) + 4 * (j & 3) + kq;
+      wa[j] = kk < F ? sW1[li * F + kk] : 0.f;
+      wb[j] = kk < F ? sW1[(16 + li) * F + kk] : 0.f;
+    }
+  }
 }
 
 // Z[i, :XS] = sum over CSR row i of X[col[e], :XS] (edges in CSR order, i.e.
@@ -908,20 +995,13 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   // ---------------- stage the graph into LDS --------------------------------
   // Only the graph and conv1's weights are staged (DMA'd straight into LDS):
   // one CU pulls ~11-30 B/cycle, so the staging time is its bytes, and the
-  // head's 64 KB of fc1 registers (row and column layouts) are loaded after
-  // the staging barrier instead, under the LDS-bound front half.
+  // head's 64 KB of fc1 registers (row and column layouts, fc1_load) are loaded
+  // after the staging barrier instead, under the LDS-bound front half.
   float fc1_row[8], fc1_col[8], fc1_bias;
-  auto load_fc1 = [&]() {
-    const int r = tid >> 3, part = tid & 7;
-    const float4 u0 = *reinterpret_cast<const float4*>(a.w.fc1w + r * 64 + part * 8);
-    const float4 u1 = *reinterpret_cast<const float4*>(a.w.fc1w + r * 64 + part * 8 + 4);
-    fc1_row[0] = u0.x; fc1_row[1] = u0.y; fc1_row[2] = u0.z; fc1_row[3] = u0.w;
-    fc1_row[4] = u1.x; fc1_row[5] = u1.y; fc1_row[6] = u1.z; fc1_row[7] = u1.w;
-    fc1_bias = a.w.fc1b[r];
-    const int o = tid & 63, rcc = dr_wave<ACC>(tid);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) fc1_col[j] = a.w.fc1w[(rcc * 8 + j) * 64 + o];
-  };
+  // conv1's B operands as a lane-ordered image in dgp (free until the head;
+  // PF stages the weights once per workgroup and reuses dgp per graph: packed rows)
+  constexpr bool IMG = DR_W1_IMAGE && KPT == 32 && !PF;
+  float* sImg = lds + c.dgp;
   float wv2, wfc[3];
   auto load_head_weights = [&]() {
     wv2 = (tid < 512) ? a.w.w2[tid] : a.w.w2e[tid - 512];
@@ -935,7 +1015,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
     }
     // fc1 last: the wait for W2 / fc2 before their LDS stores (end of the
     // front half) then leaves these 11 loads in flight (vmcnt counts in order)
-    load_fc1();
+    fc1_load(a.w, tid, wave, fc1_row, fc1_col, fc1_bias);
   };
   // (ACC: scalar loads through the constant address space — read-only for the
   // launch; hipcc cannot prove that in the accumulating loop and would use a
@@ -987,10 +1067,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   } else if (ac.first || *ac.staged == 0u) {
     stage_inputs(d, c);
   }
-  if (!PF || ac.first) {
-    dma_words(sW1, a.w.w1, 16 * F, tid, DR_DMA_ROT * 5);  // [W1; W1e] rows of F, packed
-    dma_words(sW1 + 16 * F, a.w.w1e, 16 * F, tid, DR_DMA_ROT * 14);
-  }
+  if (!PF || ac.first) w1_stage<IMG>(sW1, sImg, a.w, F, tid);  // (last: ahead of the graph's copies it was 0.3 us slower)
   // ZIN: the front half is too short to cover the head weights' latency (it
   // showed as a wait before W2's and fc2's LDS stores), so they are requested
   // here, beside the staging DMA, and arrive with it: 10.50 -> 10.25 us per
@@ -1006,6 +1083,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
       }
     for (int p = tid; p < K0 * 32; p += NT) skey[p] = 0ull;
     if (tid < 64) lds[c.p2 + tid] = 0.f;  // (TailLds::p2_zeroed)
+    w1_zero_pad<IMG>(sImg, F, tid);
   }
   // loaded late: no early wait (ACC: read once per launch by the kernel)
   if (a.p.step_counter) drop_offset = ACC ? (uint64_t)ac.step : (uint64_t)a.p.step_counter[0];
@@ -1050,12 +1128,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
     // W[li][k + 4u + kq] (wa: conv1 rows, wb: conv1_ext rows), zero past F
     constexpr int NKV = KPT / 4;
     float wa[NKV], wb[NKV];
-#pragma unroll
-    for (int j = 0; j < NKV; ++j) {
-      const int kk = 16 * (j >> 2) + 4 * (j & 3) + kq;
-      wa[j] = kk < F ? sW1[li * F + kk] : 0.f;
-      wb[j] = kk < F ? sW1[(16 + li) * F + kk] : 0.f;
-    }
+    w1_operands<KPT, IMG>(sW1, sImg, F, lane, wa, wb);
     if (PF && !ZIN) {  // the waves with no tile stage the next graph's inputs into the other buffer
       const int busy = (N + 15) >> 4;
       if (ac.next >= 0 && busy < NW && wave >= busy) {
@@ -1961,15 +2034,7 @@ __device__ __forceinline__ void tail_body(const LargeArgs& la, int b, float* lds
   STAMP(0);
 
   float fc1_row[8], fc1_col[8], fc1_bias;
-  {
-    const int r = tid >> 3, part = tid & 7;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) fc1_row[j] = a.w.fc1w[r * 64 + part * 8 + j];
-    fc1_bias = a.w.fc1b[r];
-    const int o = tid & 63, rc = tid >> 6;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) fc1_col[j] = a.w.fc1w[(rc * 8 + j) * 64 + o];
-  }
+  fc1_load(a.w, tid, tid >> 6, fc1_row, fc1_col, fc1_bias);
   const float y_g = s.y[g];
   uint64_t drop_offset = a.p.drop_offset;
   drk::dma_words<NT>(t.p1rp, s.p1_rowptr + k00 + g, K0 + 1);
@@ -2510,3 +2575,61 @@ extern "C" int dr_debug_carve_ginet_tail(const int32_t* q, char* buf, int32_t le
   return d.pos;
 }
 
+// ---- the weight registers of the graph kernels (tests/test_ginet_weight_image_host.py,
+// tests/test_gpu_ginet_weight_regs.py); debug entries, not part of the public header
+namespace {
+
+constexpr int WEIGHT_REGS_STRIDE = 49;  // per thread: fc1_row 8 | fc1_col 8 | fc1_bias | wa 16 | wb 16 (KPT = 32: 8 + 8 used)
+
+// One workgroup runs the staging and loader helpers in graph_body's order
+// (stage, request fc1, zero the pad, staging barrier, operands) and stores
+// every thread's registers.  LDS: [w1 32F | image 1 024].
+template <int KPT>
+__global__ void __launch_bounds__(NT) ginet_weight_regs_kernel(dr_ginet_weights w, int F, float* out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr bool IMG = DR_W1_IMAGE && KPT == 32;
+  constexpr int NKV = KPT / 4;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* sW1 = lds;
+  float* sImg = lds + r4(32 * F);
+  float fc1_row[8], fc1_col[8], fc1_bias;
+  w1_stage<IMG>(sW1, sImg, w, F, tid);
+  fc1_load(w, tid, wave, fc1_row, fc1_col, fc1_bias);
+  w1_zero_pad<IMG>(sImg, F, tid);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  float wa[NKV], wb[NKV];
+  w1_operands<KPT, IMG>(sW1, sImg, F, lane, wa, wb);
+  float* o = out + (int64_t)tid * WEIGHT_REGS_STRIDE;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    o[j] = fc1_row[j];
+    o[8 + j] = fc1_col[j];
+  }
+  o[16] = fc1_bias;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    o[17 + j] = j < NKV ? wa[j < NKV ? j : 0] : 0.f;
+    o[33 + j] = j < NKV ? wb[j < NKV ? j : 0] : 0.f;
+  }
+}
+
+}  // namespace
+
+// out[word] = the element of the packed [W1; W1e] (32 rows of F) that image
+// word `word` holds, or -1: zero (w1_image_src); n = 1 024 words.  Host only.
+extern "C" int dr_debug_ginet_w1_image(int32_t F, int32_t* out, int32_t n) {
+  if (F < 1 || F > 32 || !out || n != NT) return DR_E_ARG;
+  for (int wd = 0; wd < n; ++wd) out[wd] = w1_image_src(F, wd);
+  return DR_OK;
+}
+
+// out (device, NT x 49 floats; row t = thread t: fc1_row[8] | fc1_col[8] |
+// fc1_bias | wa[16] | wb[16], the KPT / 4 registers of F's kernel, then zeros)
+extern "C" int dr_debug_ginet_weight_regs(const dr_ginet_weights* w, int32_t F, float* out, int64_t n_out, void* stream) {
+  if (!w || !out || F < 1 || F > 64 || n_out < (int64_t)NT * WEIGHT_REGS_STRIDE) return DR_E_ARG;
+  const int lds_bytes = 4 * (r4(32 * F) + NT);
+  if (F <= 32) hipLaunchKernelGGL((ginet_weight_regs_kernel<32>), dim3(1), dim3(NT), lds_bytes, (hipStream_t)stream, *w, F, out);
+  else hipLaunchKernelGGL((ginet_weight_regs_kernel<64>), dim3(1), dim3(NT), lds_bytes, (hipStream_t)stream, *w, F, out);
+  return (int)hipGetLastError();
+}
