@@ -19,6 +19,13 @@ are bit for bit those of training it alone with ``FusedTrainStep``.  The store
 
 ``train_ensemble`` is the loop around it; ``kfold_indices`` and
 ``epoch_batches`` are the pure index helpers it uses.
+
+The forward side: ``FusedEnsembleForward`` runs the members' eval-mode passes
+over their batches as grids (max B_k, K) of forward-only rows of the same
+``dr_ginet_multi_pass``, one launch per step, the whole run captured into one
+HIP graph.  ``train_ensemble`` validates through it; ``predict_ensemble`` adds
+the ensemble's mean and spread (``dr_ensemble_stats``, one launch);
+``out_of_fold_predictions`` gives a cross-validation's out-of-fold scores.
 """
 
 from __future__ import annotations
@@ -67,20 +74,8 @@ class FusedEnsembleStep:
 
     def __init__(self, models, *, lr=1e-3, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8, optimizer="adam", loss="mse", loss_param=None,
                  class_weights=None, max_batch=64, process_group=None, compute_dtype="f32", fused=True):  # fmt: skip
-        models = list(models)
+        models = _check_members(models, "an ensemble step")
         k = len(models)
-        if not 1 <= k <= MAX_MEMBERS:
-            msg = f"an ensemble step takes 1 to {MAX_MEMBERS} members (got {k})"
-            raise ValueError(msg)
-        if any(type(m) is not GINet for m in models):
-            msg = f"every member must be a GINet (got {sorted({type(m).__name__ for m in models})})"
-            raise ValueError(msg)
-        if len({(m.input_shape, m.output_shape) for m in models}) != 1:
-            msg = "the members must share input_shape and output_shape"
-            raise ValueError(msg)
-        if len({id(m) for m in models}) != k:
-            msg = "the members must be distinct model objects"
-            raise ValueError(msg)
         if process_group is not None:
             msg = "the ensemble step is single-device: train data-parallel members with FusedTrainStep"
             raise ValueError(msg)
@@ -274,6 +269,7 @@ class EnsembleResult:
     train_loss: np.ndarray  # [nepoch, K]: each member's epoch loss, sum(loss * B) / count as the Trainer forms it
     val_loss: np.ndarray | None  # [nepoch, K] held-out loss, or None without val_indices
     models: list
+    val_path: str | None = None  # "fused" or "sequential": how the held-out graphs were evaluated (None without val_indices)
 
 
 def _store_of(dataset, device):
@@ -328,7 +324,415 @@ def _held_out_loss(step: FusedTrainStep, store, indices, batch_size):
     return float(total.item()) / count if count else float("nan")
 
 
-def train_ensemble(models, dataset, member_indices=None, nepoch=1, batch_size=32, shuffle=True, seed=0, val_indices=None, **step_kw):
+def _check_members(models, what):
+    """The refusals every multi-member runner makes before any device work."""
+    models = list(models)
+    k = len(models)
+    if not 1 <= k <= MAX_MEMBERS:
+        msg = f"{what} takes 1 to {MAX_MEMBERS} members (got {k})"
+        raise ValueError(msg)
+    if any(type(m) is not GINet for m in models):
+        msg = f"every member must be a GINet (got {sorted({type(m).__name__ for m in models})})"
+        raise ValueError(msg)
+    if len({(m.input_shape, m.output_shape) for m in models}) != 1:
+        msg = "the members must share input_shape and output_shape"
+        raise ValueError(msg)
+    if len({id(m) for m in models}) != k:
+        msg = "the members must be distinct model objects"
+        raise ValueError(msg)
+    return models
+
+
+def _check_batches(sizes, batches, n_graphs=None):
+    """``batches[k][s]`` as int64 arrays of graph ids, checked against the
+    batch sizes ``sizes[k][s]`` a runner was built for (and, with ``n_graphs``,
+    against the store's range).  Host only."""
+    if len(batches) != len(sizes):
+        msg = f"{len(sizes)} members, {len(batches)} lists of batches"
+        raise ValueError(msg)
+    out = []
+    for k, (want, given) in enumerate(zip(sizes, batches)):
+        arrs = [np.asarray(b, dtype=np.int64).reshape(-1) for b in given]
+        if [a.size for a in arrs] != list(want):
+            msg = f"member {k}: batches of sizes {[a.size for a in arrs]} do not match the runner's batch sizes {list(want)}"
+            raise ValueError(msg)
+        if n_graphs is not None and any(a.size and (a.min() < 0 or a.max() >= n_graphs) for a in arrs):
+            msg = f"member {k}: a graph id lies outside the store's 0..{n_graphs - 1}"
+            raise ValueError(msg)
+        out.append(arrs)
+    return out
+
+
+# Whether FusedEnsembleForward runs the multi-member launches by default (the
+# measurement behind the choice: DESIGN §5, profiles/ensemble_forward/)
+FUSED_FORWARD_DEFAULT = True
+
+
+class FusedEnsembleForward:
+    """The forward passes (eval mode: no dropout, no backward) of K GINet
+    members (1 <= K <= 8) over batches of one resident ``GraphStore``.
+
+    ``sizes[k]``: the batch sizes of member k's passes, in order; members may
+    have different numbers of batches, and a member without a batch at step s
+    sits that step out (``n_batch = 0``).  The runner owns one output buffer
+    ``[K, n_max, out_dim]``; ``run(batches)`` (``batches[k][s]``: graph ids
+    matching ``sizes``) fills it and returns the views ``[out_k[:n_k]]``.
+
+    Eligible runs (fp32, no non-finite graph in the store, every graph of the
+    store inside the per-graph kernel's LDS, no handle with ``force_large`` or
+    ``force_layers``) make each step s ONE ``dr_ginet_multi_pass``: a grid
+    (max B_k, K) of forward-only rows, Z = A x from the store when it has one,
+    LDS sized for the store's largest graph.  After one eager warm-up (Z built,
+    LDS attributes set) the whole run is captured into one HIP graph and
+    replayed (``captured = False``: the same launches, issued eagerly).
+    Otherwise, or with ``fused = False``, each member's batches run in turn
+    through the launches ``model(batch)`` makes in eval mode.  Row k of the
+    grid runs member k's own launch's code on its arguments, so both paths give
+    the same bits.  ``last_path``: "fused" or "sequential".  One exception: a
+    batch with non-finite inputs takes the layer path, which sums with torch's
+    ``index_add`` (float atomics), so its result equals ``model(batch)`` only up
+    to torch's own run-to-run differences unless
+    ``torch.use_deterministic_algorithms`` is on.
+
+    ``fused = None`` takes ``FUSED_FORWARD_DEFAULT`` (True, by the measurement
+    in DESIGN §5).  ``run`` may be called again without a device sync in
+    between: it waits for the previous run's copy of the graph ids before it
+    stages the next ones.
+
+    Nothing of a member changes: not its ``training`` flag, parameters,
+    optimizer state or device counters (a forward-only pass has no dropout and
+    no step counter).  The parameters are read through their device pointers,
+    so in-place updates (a training step between two runs) are seen.
+    """
+
+    def __init__(self, models, store, sizes, *, fused=None, captured=True):
+        from deeprank2_amd.epoch import _static_handle, descriptor_table  # noqa: PLC0415
+        from deeprank2_amd.fused import make_pass  # noqa: PLC0415
+
+        models = _check_members(models, "an ensemble forward")
+        k = len(models)
+        sizes = [[int(b) for b in s] for s in sizes]
+        if len(sizes) != k:
+            msg = f"sizes has {len(sizes)} entries for {k} members"
+            raise ValueError(msg)
+        if any(b < 1 for s in sizes for b in s):
+            msg = "every batch size must be positive"
+            raise ValueError(msg)
+        self.params = [m.ordered_params() for m in models]
+        devices = {p.device for ps in self.params for p in ps}
+        if len(devices) != 1:
+            msg = "the members must live on one device"
+            raise ValueError(msg)
+        if any(not p.is_cuda or not p.is_contiguous() or p.dtype != torch.float32 for ps in self.params for p in ps):
+            msg = "FusedEnsembleForward needs contiguous fp32 cuda parameters (no CPU fallback)"
+            raise ValueError(msg)
+        if store.device != next(iter(devices)):
+            msg = f"the members live on {next(iter(devices))}, the store on {store.device}"
+            raise ValueError(msg)
+        if store.n_feat != models[0].input_shape:
+            msg = f"the store has {store.n_feat} node features, the members expect {models[0].input_shape}"
+            raise ValueError(msg)
+        if not store.packed.has_clusters:
+            msg = "GINet pools over the stored clusters: build the dataset with clustering_method set (cluster0/cluster1 are missing)"
+            raise ValueError(msg)
+        self.models, self.store, self.sizes = models, store, sizes
+        self.spec = models[0].fused_spec
+        self.out_dim = models[0].output_shape
+        self.device = dev = store.device
+        self.fused = FUSED_FORWARD_DEFAULT if fused is None else bool(fused)
+        self.captured = bool(captured)
+        self.last_path = None  # "fused" or "sequential": which the last run() took
+        self.graph = None
+        self._staged = None  # event after the last copy out of the pinned id buffer (_load)
+        self.offs = [np.concatenate([[0], np.cumsum(s)]).astype(np.int64) for s in sizes]
+        self.n = [int(o[-1]) for o in self.offs]
+        self.n_max = max(1, *self.n)
+        self.n_steps = max(len(s) for s in sizes)
+        with torch.cuda.device(dev):
+            self.table = descriptor_table(store)
+            self.pin = torch.zeros(k * self.n_max, dtype=torch.int64, pin_memory=True)  # (rows past a member's graphs: graph 0, never read)
+            self.gids = torch.zeros(k * self.n_max, dtype=torch.int64, device=dev)
+            self.descs = torch.zeros(k, self.n_max, 64, dtype=torch.uint8, device=dev)
+            self.out = torch.zeros(k, self.n_max, self.out_dim, dtype=torch.float32, device=dev)
+        ms = store.max_sizes(np.arange(store.packed.n_graphs))
+        self.handles = [[_static_handle(store, self.descs[m, o : o + b].view(-1), b, ms) for o, b in zip(self.offs[m][:-1], sizes[m])] for m in range(k)]
+        self._probe = _static_handle(store, self.descs[0].view(-1), 1, ms)  # the store's largest graph: LDS, Z
+        self._w = [self.spec.weights(ps) for ps in self.params]
+        fwd = _lib.DR_PASS_FORWARD
+        self._passes = [[make_pass(self.out_dim, fwd, out=self.out[m, o : o + b]) for o, b in zip(self.offs[m][:-1], sizes[m])] for m in range(k)]
+        idle = [make_pass(self.out_dim, fwd, out=self.out[m]) for m in range(k)]  # a member sitting a step out: checked, never read on the device
+        self._keep = idle
+        self._members = []
+        for s in range(self.n_steps):
+            arr = (_lib.GinetMemberC * k)()
+            for m in range(k):
+                if s < len(sizes[m]):
+                    h = self.handles[m][s]
+                    arr[m].w, arr[m].pass_, arr[m].descs, arr[m].n_batch = ctypes.pointer(self._w[m]), ctypes.pointer(self._passes[m][s]), h.descs.data_ptr(), h.B
+                else:
+                    arr[m].w, arr[m].pass_, arr[m].descs, arr[m].n_batch = ctypes.pointer(self._w[m]), ctypes.pointer(idle[m]), self.descs.data_ptr(), 0
+            self._members.append(arr)
+
+    def views(self):
+        """The members' predictions as views of the runner's buffer, ``[out_k[:n_k]]``."""
+        return [self.out[m, : self.n[m]] for m in range(len(self.models))]
+
+    def eligible(self) -> bool:
+        """The run can take the multi-member launches (``FusedEnsembleStep._fits``
+        without the accumulating-pass condition, for the whole store)."""
+        nf = self.store.packed.nonfinite
+        if nf is not None and bool(np.asarray(nf).any()):
+            return False
+        if any(h.force_large or getattr(h, "force_layers", False) for hs in self.handles for h in hs):
+            return False
+        return lds_for(self.spec, self._probe, self.out_dim) <= LDS_MAX
+
+    def _load(self, batches):
+        # the previous run's copy out of the pinned buffer is only queued: a caller that never
+        # syncs (predict_ensemble's results stay on the device) runs ahead of the stream, and
+        # writing the next ids now would make that run predict them.  Wait for that copy alone
+        # (it is first in the run's queue, so this rarely blocks).
+        if self._staged is not None:
+            self._staged.synchronize()
+        host = self.pin.numpy()
+        for m, arrs in enumerate(batches):
+            if self.n[m]:
+                host[m * self.n_max : m * self.n_max + self.n[m]] = np.concatenate(arrs)
+        self.gids.copy_(self.pin, non_blocking=True)
+        if self._staged is None:
+            self._staged = torch.cuda.Event()
+        self._staged.record()
+        torch.index_select(self.table, 0, self.gids, out=self.descs.view(-1, 64))
+
+    def _launches(self):
+        """One dr_ginet_multi_pass per step (nothing is allocated here once Z exists)."""
+        lib = _lib.load()
+        store = self.store
+        z = agg_x_for(self.spec, self._probe)
+        lds = z_lds_for(self._probe, self.out_dim) if z is not None else lds_for(self.spec, self._probe, self.out_dim)
+        stream = _lib.stream_ptr(self.device)
+        for arr in self._members:
+            rc = lib.dr_ginet_multi_pass(store.cstruct(), arr, len(self.models), lds, _lib.ptr(z), store.agg_x_stride if z is not None else 0, stream)
+            _lib.check(rc, "dr_ginet_multi_pass")
+
+    def _sequential(self, batches):
+        """Each member's batches in turn, by the launches ``model(batch)`` makes
+        in eval mode (``GINet.forward``): the graph pass, or for a batch with
+        non-finite inputs the layer path with the attention computed."""
+        from deeprank2_amd import layered  # noqa: PLC0415
+        from deeprank2_amd.fused import launch  # noqa: PLC0415
+
+        with torch.no_grad():
+            for m, arrs in enumerate(batches):
+                for s, ids in enumerate(arrs):
+                    h = BatchHandle(self.store, ids.astype(np.int32))
+                    h.force_large, h.force_layers = self.handles[m][s].force_large, self.handles[m][s].force_layers
+                    if layered.needs_layers(self.spec, h, self.out_dim):
+                        o = self.offs[m][s]
+                        self.out[m, o : o + h.B].copy_(self.spec.layers(self.models[m], layered.batch_tensors(h), False))
+                    else:
+                        launch(self.spec, h, self._w[m], self._passes[m][s])
+
+    def run(self, batches):
+        """Predict ``batches[k][s]`` (arrays of graph ids of the store, sizes as
+        built) with member k; returns ``[out_k[:n_k]]``, views of the runner's
+        buffer that the next ``run`` overwrites."""
+        batches = _check_batches(self.sizes, batches, self.store.packed.n_graphs)
+        with torch.cuda.device(self.device):
+            if not (self.fused and self.eligible()):
+                self.last_path = "sequential"
+                self._sequential(batches)
+                return self.views()
+            self.last_path = "fused"
+            self._load(batches)
+            if not self.captured:
+                self._launches()
+                return self.views()
+            if self.graph is None:
+                self._launches()  # warm-up: builds Z, sets the LDS attributes; a forward changes no state
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._launches()
+                self.graph = g
+            self.graph.replay()
+        return self.views()
+
+
+@dataclass
+class EnsemblePrediction:
+    members: torch.Tensor  # [K, n, out]: every member's predictions (logits for a classifier)
+    mean: torch.Tensor  # [n, out]: regression: the members' mean; classification: their mean softmax probability
+    spread: torch.Tensor  # regression [n, out]: the unbiased standard deviation over members (NaN for K = 1); classification [n]: the entropy of ``mean``
+    label: torch.Tensor | None  # classification [n] int32: arg max of ``mean`` (-1 where it is NaN); None for regression
+    indices: np.ndarray  # [n]: the graphs predicted, in order
+
+
+ENS_KINDS = {"regress": _lib.DR_ENS_REGRESS, "classif": _lib.DR_ENS_CLASSIF}
+
+
+def ensemble_stats(members, task):
+    """``dr_ensemble_stats`` on ``members`` [K, n, out] (fp32, on the device; a
+    view whose members are more than n * out floats apart is fine): (mean,
+    spread, label) as ``EnsemblePrediction`` holds them."""
+    if task not in ENS_KINDS:
+        msg = f"task must be one of {sorted(ENS_KINDS)} (got {task!r})"
+        raise ValueError(msg)
+    _lib.require_device(members)
+    k, n, out_dim = members.shape
+    if members.dtype != torch.float32 or members.stride(2) != 1 or members.stride(1) != out_dim:
+        msg = "members must be fp32 [K, n, out] with contiguous [n, out] blocks"
+        raise ValueError(msg)
+    dev = members.device
+    classif = task == "classif"
+    with torch.cuda.device(dev):
+        mean = torch.empty(n, out_dim, dtype=torch.float32, device=dev)
+        spread = torch.empty((n,) if classif else (n, out_dim), dtype=torch.float32, device=dev)
+        label = torch.empty(n, dtype=torch.int32, device=dev) if classif else None
+        rc = _lib.load().dr_ensemble_stats(members.data_ptr(), members.stride(0), k, n, out_dim, ENS_KINDS[task], mean.data_ptr(), spread.data_ptr(), _lib.ptr(label), _lib.stream_ptr(dev))
+    _lib.check(rc, "dr_ensemble_stats")
+    return mean, spread, label
+
+
+def _device_of(models):
+    return next(iter(models[0].parameters())).device
+
+
+def predict_ensemble(models, dataset, indices=None, batch_size=64, task=None):
+    """Score graphs with every member of an ensemble: each member's
+    predictions, their mean and their spread (``EnsemblePrediction``; the
+    tensors stay on the device).
+
+    Every member predicts the same graphs: ``indices`` (default: all graphs of
+    the store), in that order, in batches of ``batch_size`` (the last one may
+    be short), through one ``FusedEnsembleForward``; one ``dr_ensemble_stats``
+    launch over its buffer then forms the statistics.  ``task``: "regress"
+    (mean and unbiased standard deviation) or "classif" (mean softmax
+    probability, its entropy, its arg-max label); default "classif" when the
+    members have more than one output.
+
+    The runner is kept with the store (``_runner_for``: the last few, with
+    their models and buffers, until ``forget_runners(store)``), so predicting
+    other graphs in batches of the same sizes replays its captured graph.  The
+    returned tensors are the caller's own (``members`` is a copy), and calls may
+    follow one another without a device sync.
+    """
+    models = _check_members(models, "an ensemble prediction")
+    if task is None:
+        task = "classif" if models[0].output_shape > 1 else "regress"
+    if task not in ENS_KINDS:
+        msg = f"task must be one of {sorted(ENS_KINDS)} (got {task!r})"
+        raise ValueError(msg)
+    store = _store_of(dataset, _device_of(models))
+    idx = np.arange(store.n_graphs, dtype=np.int64) if indices is None else np.asarray(indices, dtype=np.int64).reshape(-1)
+    batches = epoch_batches(idx, batch_size, False, 0, 0, 0)
+    runner = _runner_for(models, store, [[len(b) for b in batches]] * len(models))
+    runner.run([batches] * len(models))
+    mean, spread, label = ensemble_stats(runner.out[:, : idx.size], task)  # one launch over the runner's buffer
+    return EnsemblePrediction(runner.out[:, : idx.size].clone(), mean, spread, label, idx)
+
+
+MAX_KEPT_RUNNERS = 4
+
+
+def forget_runners(store):
+    """Drop the forward runners ``predict_ensemble`` keeps with ``store`` (and
+    with them their references to the member models, buffers and graphs)."""
+    store.__dict__.pop("_dr_ens_forward", None)
+
+
+def _runner_for(models, store, sizes):
+    """The store's ``FusedEnsembleForward`` for these members and batch sizes,
+    kept with the store (the last few) so that predicting again replays its
+    captured graph; rebuilt when a member's parameters have moved.
+
+    Lifetime: the store then holds up to ``MAX_KEPT_RUNNERS`` runners in
+    ``store._dr_ens_forward``, and with each its member models, its
+    ``[K, n_max, ...]`` device buffers, its pinned id buffer and its captured
+    graph, until the store is dropped or ``forget_runners(store)`` is called.
+    A caller who wants the lifetime in hand builds a ``FusedEnsembleForward``
+    and calls ``ensemble_stats`` on its buffer."""
+    cache = store.__dict__.setdefault("_dr_ens_forward", {})
+    key = (tuple(id(m) for m in models), tuple(tuple(int(b) for b in s) for s in sizes))
+    r = cache.get(key)
+    if r is not None and all(a is b for a, b in zip(r.models, models)) and all(p.data_ptr() == q.data_ptr() for m, ps in zip(models, r.params) for p, q in zip(m.ordered_params(), ps)):
+        return r
+    r = FusedEnsembleForward(models, store, sizes)
+    cache.pop(key, None)
+    while len(cache) >= MAX_KEPT_RUNNERS:
+        cache.pop(next(iter(cache)))
+    cache[key] = r
+    return r
+
+
+class _HeldOut:
+    """The members' held-out losses after an epoch: one ``FusedEnsembleForward``
+    over every member's ``val_indices`` (built once, run every epoch), then the
+    loss ``_held_out_loss`` forms, from the same predictions: the fp32 torch
+    loss of each batch's slice, times its length, summed in float64."""
+
+    def __init__(self, ens: FusedEnsembleStep, store, val_indices, batch_size, fused=None):
+        self.steps = ens.steps
+        self.batches = [epoch_batches(v, batch_size, False, 0, 0, 0) for v in val_indices]
+        self.runner = FusedEnsembleForward(ens.models, store, [[len(b) for b in bs] for bs in self.batches], fused=fused)
+        y = np.asarray(store.packed.y)
+        self.y = [[torch.from_numpy(y[b]).to(ens.device, torch.float32) for b in bs] for bs in self.batches]
+
+    def losses(self):
+        outs = self.runner.run(self.batches)
+        res = np.full(len(self.steps), np.nan)
+        with torch.no_grad():
+            for m, (st, out) in enumerate(zip(self.steps, outs)):
+                total = torch.zeros((), dtype=torch.float64, device=st.device)
+                o = 0
+                for b, y in zip(self.batches[m], self.y[m]):
+                    total += _mean_loss(st, out[o : o + len(b)], y).double() * len(b)
+                    o += len(b)
+                if o:
+                    res[m] = float(total.item()) / o
+        return res
+
+
+def _disjoint(val_indices, k):
+    """``val_indices`` as K int64 arrays no graph of which is listed twice."""
+    if len(val_indices) != k:
+        msg = f"val_indices needs one entry per member ({k}, got {len(val_indices)})"
+        raise ValueError(msg)
+    val = [np.asarray(v, dtype=np.int64).reshape(-1) for v in val_indices]
+    flat = np.concatenate(val) if val else np.empty(0, np.int64)
+    uniq, counts = np.unique(flat, return_counts=True)
+    if (counts > 1).any():
+        msg = f"graphs {uniq[counts > 1][:8].tolist()} are held out more than once: out-of-fold predictions need disjoint val_indices"
+        raise ValueError(msg)
+    return val
+
+
+def out_of_fold_predictions(models, dataset, val_indices, batch_size=64):
+    """The out-of-fold predictions of a cross-validation: ``(pred [G, out]
+    float32, member [G] int64)`` over the store's G graphs, row g predicted by
+    the member whose ``val_indices`` holds g (a graph no member held out: a
+    NaN row and member -1; one held out by two members: ``ValueError``).  The
+    members predict their held-out parts together, through one
+    ``FusedEnsembleForward``."""
+    models = _check_members(models, "an out-of-fold prediction")
+    val = _disjoint(val_indices, len(models))
+    store = _store_of(dataset, _device_of(models))
+    dev = store.device
+    batches = [epoch_batches(v, batch_size, False, 0, 0, 0) for v in val]
+    runner = FusedEnsembleForward(models, store, [[len(b) for b in bs] for bs in batches])
+    outs = runner.run(batches)
+    with torch.cuda.device(dev):
+        pred = torch.full((store.n_graphs, runner.out_dim), float("nan"), dtype=torch.float32, device=dev)
+        member = torch.full((store.n_graphs,), -1, dtype=torch.int64, device=dev)
+        for m, (v, o) in enumerate(zip(val, outs)):
+            if v.size:
+                rows = torch.from_numpy(v).to(dev)
+                pred.index_copy_(0, rows, o)
+                member.index_fill_(0, rows, m)
+    return pred, member
+
+
+def train_ensemble(models, dataset, member_indices=None, nepoch=1, batch_size=32, shuffle=True, seed=0, val_indices=None, val_fused=None, **step_kw):
     """Train the members together over one resident dataset.
 
     ``dataset``: a ``GraphStore``, a dataset with ``graph_store(device)``, or a
@@ -337,7 +741,9 @@ def train_ensemble(models, dataset, member_indices=None, nepoch=1, batch_size=32
     are ``epoch_batches(member_indices[k], batch_size, shuffle, seed, k,
     epoch)``; at step s every member that still has a batch s takes part and
     the others sit out.  ``val_indices[k]`` (optional): member k's held-out
-    graphs, evaluated after every epoch.  ``step_kw`` goes to
+    graphs, evaluated after every epoch through one ``FusedEnsembleForward``
+    (``val_fused``: its ``fused``; ``EnsembleResult.val_path`` says which path
+    ran), or with ``fused = False`` by each member's own loop.  ``step_kw`` goes to
     ``FusedEnsembleStep``.  Training member k alone with ``FusedTrainStep`` over
     the same batches gives the same parameters and losses, bit for bit.
     """
@@ -353,6 +759,9 @@ def train_ensemble(models, dataset, member_indices=None, nepoch=1, batch_size=32
         raise ValueError(msg)
     train_loss = np.full((nepoch, k), np.nan)
     val_loss = None if val_indices is None else np.full((nepoch, k), np.nan)
+    # the held-out graphs of all members through one forward runner, built once
+    # (fused = False: the members' own eval-mode loops, one after another)
+    val = _HeldOut(ens, store, val_indices, batch_size, val_fused) if val_indices is not None and ens.fused else None
     for epoch in range(nepoch):
         batches = [epoch_batches(member_indices[m], batch_size, shuffle, seed, m, epoch) for m in range(k)]
         loss_sum = torch.zeros(k, dtype=torch.float64, device=ens.device)
@@ -368,7 +777,10 @@ def train_ensemble(models, dataset, member_indices=None, nepoch=1, batch_size=32
         for m in range(k):
             if count[m]:
                 train_loss[epoch, m] = float(total[m]) / int(count[m])
-        if val_indices is not None:
+        if val is not None:
+            val_loss[epoch] = val.losses()
+        elif val_indices is not None:
             for m in range(k):
                 val_loss[epoch, m] = _held_out_loss(ens.steps[m], store, val_indices[m], batch_size)
-    return EnsembleResult(train_loss, val_loss, models)
+    val_path = None if val_indices is None else "sequential" if val is None else val.runner.last_path
+    return EnsembleResult(train_loss, val_loss, models, val_path)

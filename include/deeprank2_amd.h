@@ -778,6 +778,38 @@ int dr_reduce_multi_build(const dr_reduce_member* members, int32_t n_members, vo
 int dr_reduce_update_multi(const void* dev_args, int32_t n_members, int32_t n_blocks, int32_t opt_kind,
                            void* stream);
 
+/* The ensemble's answer from its members' predictions.  out holds member k's
+ * predictions [n, out_dim] at out + k * member_stride (in floats; the buffer a
+ * grid of forward-only dr_ginet_multi_pass rows fills).  One thread per graph
+ * walks the members in the order k = 0 .. n_members-1: no atomics, no
+ * cross-thread reduction, so the result does not depend on the launch shape.
+ * All arithmetic is fp32.
+ *   DR_ENS_REGRESS  mean [n, out_dim]:   s = o_0; s += o_k (k = 1 .. K-1); then
+ *                   s / (float)K -- the adds and the divide separate, correctly
+ *                   rounded operations.
+ *                   spread [n, out_dim]: the unbiased standard deviation, two
+ *                   passes: sqrt(sum_k (o_k - mean)^2 / (K - 1)) in the same
+ *                   member order; K = 1 gives NaN (0 / 0), as torch.std does.
+ *                   A NaN in any member propagates to both.  label is not
+ *                   touched and may be NULL.
+ *   DR_ENS_CLASSIF  per member p_k = softmax(o_k) over out_dim (the row
+ *                   maximum subtracted).
+ *                   mean [n, out_dim]: the mean of p_k, by the chain above.
+ *                   spread [n]: the entropy of that mean, -sum_c p_c log p_c
+ *                   (natural log); a term with p_c == 0 contributes 0.
+ *                   label [n]: the lowest class index attaining the maximum of
+ *                   the mean; -1 when any p_c is NaN (a NaN logit makes its
+ *                   member's whole row, hence the mean's, NaN).
+ * Checked before any device work, DR_E_ARG for: a NULL out, mean or spread; a
+ * NULL label with DR_ENS_CLASSIF; n_members outside 1..DR_MAX_MEMBERS; out_dim
+ * outside 1..DR_MAX_OUT; n < 0; member_stride < n * out_dim when n_members > 1;
+ * an unknown kind.  DR_OK without a launch for n == 0.  No allocation, copy or
+ * sync: capturable.                                                          */
+#define DR_ENS_REGRESS 0
+#define DR_ENS_CLASSIF 1
+int dr_ensemble_stats(const float* out, int64_t member_stride, int32_t n_members, int32_t n, int32_t out_dim,
+                      int32_t kind, float* mean, float* spread, int32_t* label, void* stream);
+
 /* ---- generic layer kernels (arbitrary edge lists; GINetConvLayer API) ---- */
 
 /* Stable CSR of (row, col) pairs sorted by row: rowptr [n_rows+1], perm [E]
