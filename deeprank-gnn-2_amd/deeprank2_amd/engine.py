@@ -35,7 +35,7 @@ import ctypes
 import torch
 
 from deeprank2_amd import _lib, layered
-from deeprank2_amd.fused import BatchHandle, _device_cus, agg_x_for, launch, lds_for, param_table, slab_rows_for, z_lds_for
+from deeprank2_amd.fused import BatchHandle, _device_cus, agg_x_for, capture_after_warmup, launch, lds_for, param_table, slab_rows_for, z_lds_for
 from deeprank2_amd.neuralnets.gnn.ginet import acc_recipe
 
 
@@ -587,13 +587,7 @@ class FusedTrainStep:
         changed is rolled back."""
         self._packed()  # made before the snapshot, so the restore covers it
         with self._state_kept():
-            steps()
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                steps()
-            torch.cuda.synchronize(self.device)
-        return g
+            return capture_after_warmup(steps, self.device)
 
     def capture_sweep(self, handles, global_batch=None):
         """Capture one training step per handle, in order, into ONE HIP graph

@@ -38,10 +38,12 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from deeprank2_amd import _lib
+from deeprank2_amd import _lib, layered
 from deeprank2_amd.engine import LOSS_KINDS, OPT_KINDS, FusedTrainStep
-from deeprank2_amd.fused import LDS_MAX, BatchHandle, agg_x_for, lds_for, slab_rows_for, z_lds_for
+from deeprank2_amd.epoch import StagedBatches, store_fits
+from deeprank2_amd.fused import LDS_MAX, BatchHandle, agg_x_for, capture_after_warmup, launch, lds_for, make_pass, slab_rows_for, z_lds_for
 from deeprank2_amd.neuralnets.gnn.ginet import GINet
+from deeprank2_amd.store import GraphStore, pack_graphs
 
 MAX_MEMBERS = _lib.DR_MAX_MEMBERS
 
@@ -230,12 +232,7 @@ class FusedEnsembleStep:
             for st in self.steps:
                 es.enter_context(st._state_kept())  # noqa: SLF001
             losses = self.losses.clone()
-            self.step(handles, dropout=dropout)
-            torch.cuda.synchronize(self.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self.step(handles, dropout=dropout)
-            torch.cuda.synchronize(self.device)
+            g = capture_after_warmup(lambda: self.step(handles, dropout=dropout), self.device)
         self.losses.copy_(losses)
         return g
 
@@ -273,8 +270,6 @@ class EnsembleResult:
 
 
 def _store_of(dataset, device):
-    from deeprank2_amd.store import GraphStore, pack_graphs  # noqa: PLC0415
-
     if isinstance(dataset, GraphStore):
         return dataset
     if callable(getattr(dataset, "graph_store", None)):
@@ -304,24 +299,34 @@ def _mean_loss(step: FusedTrainStep, out, y):
     return fn.huber_loss(pred, y, delta=step.loss_param)
 
 
+def _weighted_mean_loss(step: FusedTrainStep, triples):
+    """The step's loss over the batches ``triples`` yields as (out, y, len):
+    each batch's fp32 torch loss times its length, summed in float64 on the
+    device (one ``.item()``), over the graph count; NaN without a graph."""
+    total = torch.zeros((), dtype=torch.float64, device=step.device)
+    count = 0
+    with torch.no_grad():
+        for out, y, n in triples:
+            total += _mean_loss(step, out, y).double() * n
+            count += n
+    return float(total.item()) / count if count else float("nan")
+
+
 def _held_out_loss(step: FusedTrainStep, store, indices, batch_size):
     """Member's loss over ``indices`` through its forward-only pass (eval mode: no dropout)."""
     model = step.model
     was_training = model.training
     model.eval()
-    total = torch.zeros((), dtype=torch.float64, device=step.device)
-    count = 0
+
+    def triples():  # (run from inside the helper's no_grad)
+        for idx in epoch_batches(indices, batch_size, False, 0, 0, 0):
+            y = torch.from_numpy(np.asarray(store.packed.y)[idx]).to(step.device, torch.float32)
+            yield model(_Handle(BatchHandle(store, idx.astype(np.int32)))), y, len(idx)
+
     try:
-        with torch.no_grad():
-            for idx in epoch_batches(indices, batch_size, False, 0, 0, 0):
-                h = BatchHandle(store, idx.astype(np.int32))
-                out = model(_Handle(h))
-                y = torch.from_numpy(np.asarray(store.packed.y)[idx]).to(step.device, torch.float32)
-                total += _mean_loss(step, out, y).double() * len(idx)
-                count += len(idx)
+        return _weighted_mean_loss(step, triples())
     finally:
         model.train(was_training)
-    return float(total.item()) / count if count else float("nan")
 
 
 def _check_members(models, what):
@@ -406,9 +411,6 @@ class FusedEnsembleForward:
     """
 
     def __init__(self, models, store, sizes, *, fused=None, captured=True):
-        from deeprank2_amd.epoch import _static_handle, descriptor_table  # noqa: PLC0415
-        from deeprank2_amd.fused import make_pass  # noqa: PLC0415
-
         models = _check_members(models, "an ensemble forward")
         k = len(models)
         sizes = [[int(b) for b in s] for s in sizes]
@@ -443,34 +445,24 @@ class FusedEnsembleForward:
         self.captured = bool(captured)
         self.last_path = None  # "fused" or "sequential": which the last run() took
         self.graph = None
-        self._staged = None  # event after the last copy out of the pinned id buffer (_load)
-        self.offs = [np.concatenate([[0], np.cumsum(s)]).astype(np.int64) for s in sizes]
-        self.n = [int(o[-1]) for o in self.offs]
-        self.n_max = max(1, *self.n)
-        self.n_steps = max(len(s) for s in sizes)
+        self.staged = st = StagedBatches(store, sizes)
+        self.handles, self.offs, self.n, self._probe = st.handles, st.offs, st.n, st.probe  # (the probe: the store's largest graph, for LDS and Z)
         with torch.cuda.device(dev):
-            self.table = descriptor_table(store)
-            self.pin = torch.zeros(k * self.n_max, dtype=torch.int64, pin_memory=True)  # (rows past a member's graphs: graph 0, never read)
-            self.gids = torch.zeros(k * self.n_max, dtype=torch.int64, device=dev)
-            self.descs = torch.zeros(k, self.n_max, 64, dtype=torch.uint8, device=dev)
-            self.out = torch.zeros(k, self.n_max, self.out_dim, dtype=torch.float32, device=dev)
-        ms = store.max_sizes(np.arange(store.packed.n_graphs))
-        self.handles = [[_static_handle(store, self.descs[m, o : o + b].view(-1), b, ms) for o, b in zip(self.offs[m][:-1], sizes[m])] for m in range(k)]
-        self._probe = _static_handle(store, self.descs[0].view(-1), 1, ms)  # the store's largest graph: LDS, Z
+            self.out = torch.zeros(k, st.n_max, self.out_dim, dtype=torch.float32, device=dev)
         self._w = [self.spec.weights(ps) for ps in self.params]
         fwd = _lib.DR_PASS_FORWARD
         self._passes = [[make_pass(self.out_dim, fwd, out=self.out[m, o : o + b]) for o, b in zip(self.offs[m][:-1], sizes[m])] for m in range(k)]
         idle = [make_pass(self.out_dim, fwd, out=self.out[m]) for m in range(k)]  # a member sitting a step out: checked, never read on the device
         self._keep = idle
         self._members = []
-        for s in range(self.n_steps):
+        for s in range(st.n_steps):
             arr = (_lib.GinetMemberC * k)()
             for m in range(k):
                 if s < len(sizes[m]):
                     h = self.handles[m][s]
                     arr[m].w, arr[m].pass_, arr[m].descs, arr[m].n_batch = ctypes.pointer(self._w[m]), ctypes.pointer(self._passes[m][s]), h.descs.data_ptr(), h.B
                 else:
-                    arr[m].w, arr[m].pass_, arr[m].descs, arr[m].n_batch = ctypes.pointer(self._w[m]), ctypes.pointer(idle[m]), self.descs.data_ptr(), 0
+                    arr[m].w, arr[m].pass_, arr[m].descs, arr[m].n_batch = ctypes.pointer(self._w[m]), ctypes.pointer(idle[m]), st.descs.data_ptr(), 0
             self._members.append(arr)
 
     def views(self):
@@ -480,29 +472,9 @@ class FusedEnsembleForward:
     def eligible(self) -> bool:
         """The run can take the multi-member launches (``FusedEnsembleStep._fits``
         without the accumulating-pass condition, for the whole store)."""
-        nf = self.store.packed.nonfinite
-        if nf is not None and bool(np.asarray(nf).any()):
+        if any(h.force_large or h.force_layers for hs in self.handles for h in hs):
             return False
-        if any(h.force_large or getattr(h, "force_layers", False) for hs in self.handles for h in hs):
-            return False
-        return lds_for(self.spec, self._probe, self.out_dim) <= LDS_MAX
-
-    def _load(self, batches):
-        # the previous run's copy out of the pinned buffer is only queued: a caller that never
-        # syncs (predict_ensemble's results stay on the device) runs ahead of the stream, and
-        # writing the next ids now would make that run predict them.  Wait for that copy alone
-        # (it is first in the run's queue, so this rarely blocks).
-        if self._staged is not None:
-            self._staged.synchronize()
-        host = self.pin.numpy()
-        for m, arrs in enumerate(batches):
-            if self.n[m]:
-                host[m * self.n_max : m * self.n_max + self.n[m]] = np.concatenate(arrs)
-        self.gids.copy_(self.pin, non_blocking=True)
-        if self._staged is None:
-            self._staged = torch.cuda.Event()
-        self._staged.record()
-        torch.index_select(self.table, 0, self.gids, out=self.descs.view(-1, 64))
+        return store_fits(self.spec, self.store, self.out_dim, self._probe)
 
     def _launches(self):
         """One dr_ginet_multi_pass per step (nothing is allocated here once Z exists)."""
@@ -519,9 +491,6 @@ class FusedEnsembleForward:
         """Each member's batches in turn, by the launches ``model(batch)`` makes
         in eval mode (``GINet.forward``): the graph pass, or for a batch with
         non-finite inputs the layer path with the attention computed."""
-        from deeprank2_amd import layered  # noqa: PLC0415
-        from deeprank2_amd.fused import launch  # noqa: PLC0415
-
         with torch.no_grad():
             for m, arrs in enumerate(batches):
                 for s, ids in enumerate(arrs):
@@ -544,17 +513,12 @@ class FusedEnsembleForward:
                 self._sequential(batches)
                 return self.views()
             self.last_path = "fused"
-            self._load(batches)
+            self.staged.load(batches)
             if not self.captured:
                 self._launches()
                 return self.views()
-            if self.graph is None:
-                self._launches()  # warm-up: builds Z, sets the LDS attributes; a forward changes no state
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._launches()
-                self.graph = g
+            if self.graph is None:  # (the warm-up builds Z; a forward changes no state: nothing to put back)
+                self.graph = capture_after_warmup(self._launches, self.device)
             self.graph.replay()
         return self.views()
 
@@ -680,17 +644,10 @@ class _HeldOut:
 
     def losses(self):
         outs = self.runner.run(self.batches)
-        res = np.full(len(self.steps), np.nan)
-        with torch.no_grad():
-            for m, (st, out) in enumerate(zip(self.steps, outs)):
-                total = torch.zeros((), dtype=torch.float64, device=st.device)
-                o = 0
-                for b, y in zip(self.batches[m], self.y[m]):
-                    total += _mean_loss(st, out[o : o + len(b)], y).double() * len(b)
-                    o += len(b)
-                if o:
-                    res[m] = float(total.item()) / o
-        return res
+        res = []
+        for st, out, offs, ys in zip(self.steps, outs, self.runner.offs, self.y):
+            res.append(_weighted_mean_loss(st, ((out[o : o + len(y)], y, len(y)) for o, y in zip(offs, ys))))
+        return np.array(res)
 
 
 def _disjoint(val_indices, k):

@@ -46,26 +46,7 @@ import numpy as np
 import torch
 
 from deeprank2_amd import _lib
-from deeprank2_amd.fused import LDS_MAX, BatchHandle, lds_for
-
-
-def _static_handle(store, descs, b, max_sizes):
-    """A BatchHandle over a fixed descriptor buffer (its graphs change between
-    replays; everything sized from it is sized for the dataset's largest graph)."""
-    h = BatchHandle.__new__(BatchHandle)
-    h.store = store
-    h.gids_host = np.zeros(b, dtype=np.int32)  # placeholder: no eligible path reads the ids on the host
-    h.gids = None
-    h.descs = descs
-    h.B = int(b)
-    h.max_sizes = max_sizes
-    h.nonfinite = False
-    h._lds = {}  # noqa: SLF001
-    h.force_large = h.force_layers = False
-    h.large_tile = h.vanilla_split = h.fault = None
-    h.large_halos = h.large_atomic_max = h.vanilla_words = True
-    h.vanilla_tile_rows = 0
-    return h
+from deeprank2_amd.fused import LDS_MAX, BatchHandle, capture_after_warmup, launch, lds_for, make_pass
 
 
 def descriptor_table(store):
@@ -85,11 +66,69 @@ def eligible(step, store) -> bool:
         return False
     if step.loss == "ce" and step.class_weights is not None:
         return False
+    return store_fits(spec, store, step.out_dim)
+
+
+def store_fits(spec, store, out_dim, probe=None) -> bool:
+    """No graph of the store is non-finite and its largest graph fits the
+    per-graph kernel's LDS: any batch of it takes the one launch a captured
+    run holds (``probe``: a runner's own, whose cached LDS size is reused)."""
     nf = store.packed.nonfinite
     if nf is not None and bool(np.asarray(nf).any()):
         return False
-    probe = _static_handle(store, None, 1, store.max_sizes(np.arange(store.packed.n_graphs)))
-    return lds_for(spec, probe, step.out_dim) <= LDS_MAX
+    if probe is None:
+        probe = BatchHandle.fixed(store, None, 1, store.max_sizes(np.arange(store.packed.n_graphs)))
+    return lds_for(spec, probe, out_dim) <= LDS_MAX
+
+
+class StagedBatches:
+    """The graph ids of a captured run, staged for its replays: ``sizes[r][s]``
+    is the size of row r's batch s (a row: an ensemble member; one row for an
+    epoch or an evaluation).  ``load(batches)`` is one pinned host->device copy
+    of the ids and one gather out of the store's descriptor table into the
+    fixed buffer ``descs`` [R, n_max, 64] that ``handles[r][s]`` view; ``probe``
+    is a one-graph handle sized for the store's largest graph.  The buffers
+    start zeroed: rows past a row's last graph gather graph 0 and are never read."""
+
+    @staticmethod
+    def layout(sizes):
+        """(offs [R][len + 1], n [R], n_max >= 1, n_steps) of ``sizes``."""
+        offs = [np.concatenate([[0], np.cumsum(s)]).astype(np.int64) for s in sizes]
+        n = [int(o[-1]) for o in offs]
+        return offs, n, max(1, *n), max(len(s) for s in sizes)
+
+    def __init__(self, store, sizes):
+        self.offs, self.n, self.n_max, self.n_steps = self.layout(sizes)
+        rows, dev = len(sizes), store.device
+        with torch.cuda.device(dev):
+            self.table = descriptor_table(store)
+            self.pin = torch.zeros(rows, self.n_max, dtype=torch.int64, pin_memory=True)
+            self.gids = torch.zeros(rows, self.n_max, dtype=torch.int64, device=dev)
+            self.descs = torch.zeros(rows, self.n_max, 64, dtype=torch.uint8, device=dev)
+        ms = store.max_sizes(np.arange(store.packed.n_graphs))
+        self.handles = [[BatchHandle.fixed(store, self.descs[r, o : o + b].view(-1), b, ms) for o, b in zip(self.offs[r][:-1], sizes[r])] for r in range(rows)]
+        self.probe = BatchHandle.fixed(store, self.descs[0].view(-1), 1, ms)
+        self._copied = None  # event behind the last load's copy out of the pinned buffer
+
+    def load(self, batches):
+        """Stage ``batches[r][s]`` (graph ids, sizes as built).  The previous
+        load's copy out of the pinned buffer is only queued: a caller that never
+        syncs runs ahead of the stream, and writing the next ids now would make
+        that run read them.  So wait for that copy (with its gather it is first
+        in its run's queue: this rarely blocks).  The event is recorded behind
+        the gather, not between the copy and the gather: measured 3 us cheaper
+        per run (profiles/runner_refactor/event_position.txt)."""
+        if self._copied is None:
+            self._copied = torch.cuda.Event()
+        else:
+            self._copied.synchronize()
+        host = self.pin.numpy()
+        for r, arrs in enumerate(batches):
+            if self.n[r]:
+                host[r, : self.n[r]] = np.concatenate([np.asarray(a) for a in arrs])
+        self.gids.copy_(self.pin, non_blocking=True)
+        torch.index_select(self.table, 0, self.gids.view(-1), out=self.descs.view(-1, 64))
+        self._copied.record()
 
 
 class EpochRunner:
@@ -100,14 +139,9 @@ class EpochRunner:
         self.sizes = [int(s) for s in sizes]
         # the loss scale of a data-parallel step is 1/(global batch)
         self.global_sizes = self.sizes if global_sizes is None else [int(s) for s in global_sizes]
-        self.offs = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
-        n, dev = int(self.offs[-1]), step.device
-        self.table = descriptor_table(store)
-        self.pin = torch.empty(n, dtype=torch.int64, pin_memory=True)
-        self.gids = torch.empty(n, dtype=torch.int64, device=dev)
-        self.descs = torch.empty(n, 64, dtype=torch.uint8, device=dev)
-        ms = store.max_sizes(np.arange(store.packed.n_graphs))
-        self.handles = [_static_handle(store, self.descs[o : o + b].view(-1), b, ms) for o, b in zip(self.offs[:-1], self.sizes)]
+        self.staged = StagedBatches(store, [self.sizes])
+        self.handles, self.offs = self.staged.handles[0], self.staged.offs[0]
+        n, dev = self.staged.n[0], step.device
         self.out = torch.empty(n, step.out_dim, dtype=torch.float32, device=dev)
         self.loss = torch.empty(len(self.sizes), dtype=torch.float32, device=dev)
         self.graph = None
@@ -131,11 +165,6 @@ class EpochRunner:
                 p.out = v
             s.loss_out = saved[1]
 
-    def _load(self, order):
-        self.pin.copy_(torch.from_numpy(np.asarray(order, dtype=np.int64)))
-        self.gids.copy_(self.pin, non_blocking=True)
-        torch.index_select(self.table, 0, self.gids, out=self.descs)
-
     def run(self, batches):
         """Train on ``batches`` (lists of dataset positions = graph ids of the
         store, sizes as built); returns (per-batch losses [nb], predictions
@@ -143,29 +172,17 @@ class EpochRunner:
         if [len(b) for b in batches] != self.sizes:
             msg = "epoch batches do not match the runner's batch sizes"
             raise ValueError(msg)
-        self._load(np.concatenate([np.asarray(b) for b in batches]) if batches else [])
+        self.staged.load([batches])
         s = self.step
         if self.graph is None:
             # the first use: eager warm-up steps (LDS attributes, the allocator),
             # the capture, the training state put back, then the real replay
-            s._packed()  # noqa: SLF001
             if s.pg is not None:
                 # the loss terms go to the epoch's loss vector (summed over the
                 # ranks once per epoch): the flat buffer's loss slot, all-reduced
                 # with the gradients every step, stays zero
                 s.loss_out.zero_()
-            snap = [t.detach().clone() for t in s._state_tensors()]  # noqa: SLF001
-            n0 = s.step_count
-            self._steps()
-            torch.cuda.synchronize(s.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._steps()
-            torch.cuda.synchronize(s.device)
-            for t, v in zip(s._state_tensors(), snap):  # noqa: SLF001
-                t.data.copy_(v)
-            s.step_count = n0
-            self.graph = g
+            self.graph = s._capture_steps(self._steps)  # noqa: SLF001
         self.graph.replay()
         s.step_count += len(self.sizes)
         return self.loss, self.out
@@ -196,23 +213,15 @@ class EvalRunner:
         self.model, self.store = model, store
         self.spec = model.fused_spec
         self.sizes = [int(s) for s in sizes]
-        self.offs = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
-        n, dev = int(self.offs[-1]), store.device
         self.out_dim = model.output_shape
-        self.table = descriptor_table(store)
-        self.pin = torch.empty(n, dtype=torch.int64, pin_memory=True)
-        self.gids = torch.empty(n, dtype=torch.int64, device=dev)
-        self.descs = torch.empty(n, 64, dtype=torch.uint8, device=dev)
-        ms = store.max_sizes(np.arange(store.packed.n_graphs))
-        self.handles = [_static_handle(store, self.descs[o : o + b].view(-1), b, ms) for o, b in zip(self.offs[:-1], self.sizes)]
-        self.out = torch.empty(n, self.out_dim, dtype=torch.float32, device=dev)
+        self.staged = StagedBatches(store, [self.sizes])
+        self.handles, self.offs = self.staged.handles[0], self.staged.offs[0]
+        self.out = torch.empty(self.staged.n[0], self.out_dim, dtype=torch.float32, device=store.device)
         self.params = model.ordered_params()
         self.w = self.spec.weights(self.params)  # device pointers: Adam updates the parameters in place
         self.graph = None
 
     def _passes(self):
-        from deeprank2_amd.fused import launch, make_pass  # noqa: PLC0415
-
         for h, o, b in zip(self.handles, self.offs[:-1], self.sizes):
             launch(self.spec, h, self.w, make_pass(self.out_dim, _lib.DR_PASS_FORWARD, out=self.out[o : o + b]))
 
@@ -220,16 +229,9 @@ class EvalRunner:
         if [len(b) for b in batches] != self.sizes:
             msg = "evaluation batches do not match the runner's batch sizes"
             raise ValueError(msg)
-        self.pin.copy_(torch.from_numpy(np.concatenate([np.asarray(b) for b in batches]).astype(np.int64)))
-        self.gids.copy_(self.pin, non_blocking=True)
-        torch.index_select(self.table, 0, self.gids, out=self.descs)
-        if self.graph is None:
-            self._passes()  # warm-up (LDS attributes, the allocator); a forward changes no state
-            torch.cuda.synchronize(self.store.device)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._passes()
-            self.graph = g
+        self.staged.load([batches])
+        if self.graph is None:  # (a forward changes no state: nothing to put back after the warm-up)
+            self.graph = capture_after_warmup(self._passes, self.store.device)
         self.graph.replay()
         return self.out
 
@@ -238,11 +240,7 @@ def eval_eligible(model, store) -> bool:
     spec = getattr(model, "fused_spec", None)
     if spec is None or spec.run is not None or model.training:
         return False
-    nf = store.packed.nonfinite
-    if nf is not None and bool(np.asarray(nf).any()):
-        return False
-    probe = _static_handle(store, None, 1, store.max_sizes(np.arange(store.packed.n_graphs)))
-    return lds_for(spec, probe, model.output_shape) <= LDS_MAX
+    return store_fits(spec, store, model.output_shape)
 
 
 def eval_runner_for(model, store, sizes, cache: dict):

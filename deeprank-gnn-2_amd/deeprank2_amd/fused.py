@@ -34,6 +34,27 @@ class BatchHandle:
         self.max_sizes = store.max_sizes(self.gids_host)
         nf = store.packed.nonfinite
         self.nonfinite = bool(nf is not None and nf[self.gids_host.astype(np.int64)].any())
+        self._knob_defaults()
+
+    @classmethod
+    def fixed(cls, store: GraphStore, descs, b, max_sizes):
+        """A handle over a fixed descriptor buffer ``descs`` of ``b`` graphs,
+        whose graphs change between the replays of a captured run (epoch.py):
+        everything sized from it is sized for ``max_sizes`` (the store's largest
+        graph), and no path such a run takes reads the ids on the host."""
+        h = cls.__new__(cls)
+        h.store = store
+        h.gids_host = np.zeros(b, dtype=np.int32)  # placeholder
+        h.gids = None
+        h.descs = descs
+        h.B = int(b)
+        h.max_sizes = max_sizes
+        h.nonfinite = False
+        h._knob_defaults()
+        return h
+
+    def _knob_defaults(self):
+        """The per-batch caches and diagnostic knobs of a new handle (both constructors)."""
         self._lds = {}
         self.force_large = False  # run the split (tile + tail) path on small graphs too
         self.large_tile = None  # nodes per tile of the split path (default 128)
@@ -464,6 +485,19 @@ def launch(spec: FusedSpec, h: BatchHandle, w, p, wpack=None):
     else:
         msg = f"largest graph of the batch needs {lds} B of LDS (> 160 KiB) and {spec.entry} has no large-graph path"
         raise RuntimeError(msg)
+
+
+def capture_after_warmup(launches, device):
+    """``launches()`` once eagerly (warm-up: LDS attributes, plans, Z, the
+    allocator), then captured into a HIP graph (``torch.cuda.CUDAGraph``),
+    which is returned.  A caller whose launches change state rolls it back."""
+    launches()
+    torch.cuda.synchronize(device)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        launches()
+    torch.cuda.synchronize(device)
+    return g
 
 
 def _device_cus(device):
