@@ -1308,6 +1308,102 @@ __global__ void __launch_bounds__(NT) ginet_graph_kernel(GinetArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// Input gradients (dr_ginet_input_grad_pass): the training pass of
+// ginet_graph_kernel, then dX = d(out . dout) / dx from the LDS state its
+// backward leaves.  Conv1 is H = relu((A X) [W1; W1e]^T) and the depth-0 max
+// pool routes each (cluster, channel)'s gradient to its one winning node, so
+//   dZ[i, :] = sum over (k, ch) with a1[k, ch] = i of dp1[k, ch] * Wcat[ch, :F]
+// has at most 32 K0 non-zero rows (a node belongs to one cluster: rows of
+// different clusters never collide), and dX = A^T dZ is the front half's CSR
+// gather over the store's transposed CSR (t_rowptr, t_col: stable, so each row
+// sums its in-edges in the original edge order).
+// The transposed CSR in LDS: the gather form reuses its rp / col regions (same
+// sizes, dead after the front half); the Z-input form has none and appends
+// them after the carve.
+// ---------------------------------------------------------------------------
+struct IgLds {
+  int trp, tcol, total;
+};
+__host__ __device__ inline IgLds ig_lds(const Carve& c, int N, int E, int zs) {
+  IgLds g;
+  if (zs > 0) {
+    g.trp = c.total;
+    g.tcol = g.trp + r4(N + 1);
+    g.total = g.tcol + r4((E + 1) / 2);
+  } else {
+    g.trp = c.rp;
+    g.tcol = c.col;
+    g.total = c.total;
+  }
+  return g;
+}
+
+template <int KPT, bool ZIN>
+__global__ void __launch_bounds__(NT) ginet_input_grad_kernel(GinetArgs a, dr_input_grad ig) {
+  extern __shared__ __attribute__((aligned(16))) float lds_raw[];
+  graph_body<KPT, false, false, ZIN>(a, AccCtx{});
+  __syncthreads();  // the tail's last step (dW1) has read Z; dp1 / a1 are complete
+  float* lds = lds_raw;
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const dr_graph_desc d = a.descs[b];
+  const int N = d.n_nodes, E = d.n_edges, K0 = d.n_k0, F = a.s.n_feat;
+  const int zs = ZIN ? a.z_stride : 0;
+  const Carve c = carve(N, E, F, K0, d.n_p1, d.n_k1, a.s.transpose_aliased, a.p.out_dim, zs);
+  const IgLds g = ig_lds(c, N, E, zs);
+  // dZ in the Z region, rows of DS = r4(F) words (16-byte rows for the gather's
+  // reads, DS <= LDW in both forms; columns F .. DS - 1 stay zero)
+  float* dZ = lds + c.z;
+  const int DS = c.XS;
+  int* trp = reinterpret_cast<int*>(lds + g.trp);
+  uint16_t* tcol = reinterpret_cast<uint16_t*>(lds + g.tcol);
+  const float* dp1 = lds + c.dp1;
+  const int* a1 = reinterpret_cast<const int*>(lds + c.a1);
+  for (int p = tid; p < N * c.LDW; p += NT) dZ[p] = 0.f;
+  dma_words(trp, a.s.t_rowptr + d.node0 + d.gid, N + 1, tid);
+  dma_x4(tcol, a.s.t_col + d.col0, (E + 7) / 8, tid, 7);
+  const int64_t row0 = ig.row_off[b];
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  // one thread per (cluster k, feature f), channels in ascending order: no two
+  // threads touch one word (k fixes the node's cluster, f the column), and the
+  // order of the fmaf chain into a word is fixed
+  for (int p = tid; p < K0 * F; p += NT) {
+    const int k = p / F, f = p - k * F;
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const float* wsrc = (hf ? a.w.w1e : a.w.w1) + f;
+      float w[16], v[16];
+      int i[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) w[u] = wsrc[u * F];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int4 iv = *reinterpret_cast<const int4*>(a1 + k * 32 + hf * 16 + 4 * q);
+        const float4 vv = *reinterpret_cast<const float4*>(dp1 + k * 32 + hf * 16 + 4 * q);
+        i[4 * q] = iv.x; i[4 * q + 1] = iv.y; i[4 * q + 2] = iv.z; i[4 * q + 3] = iv.w;
+        v[4 * q] = vv.x; v[4 * q + 1] = vv.y; v[4 * q + 2] = vv.z; v[4 * q + 3] = vv.w;
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (i[u] < N) dZ[i[u] * DS + f] = fmaf(v[u], w[u], dZ[i[u] * DS + f]);
+    }
+  }
+  __syncthreads();
+  // dX[m, :] = sum over transposed row m, in slot order from +0, of dZ[t_col[s], :]
+  // (8 lanes per row, one 16-byte chunk each); zeros past r4(F)
+  const int sub = tid & 7, nchd = DS >> 2, ncho = ig.dx_stride >> 2;
+  for (int m = tid >> 3; m < N; m += NT / 8) {
+    const int eb = trp[m], ee = trp[m + 1];
+    float* row = ig.dx + (row0 + m) * (int64_t)ig.dx_stride;
+    for (int ch = sub; ch < ncho; ch += 8) {
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (ch < nchd) acc = drk::gather_row_chunk_lds(tcol, eb, ee, dZ, DS, ch * 4);
+      *reinterpret_cast<float4*>(row + ch * 4) = acc;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Several members in one launch (dr_ginet_multi_pass): a batch of 64 graphs
 // occupies 64 of the 256 CUs for the length of one graph's chain of phases, so
 // up to DR_MAX_MEMBERS independent models (an ensemble, the folds of a
@@ -2213,6 +2309,53 @@ extern "C" int dr_ginet_graph_pass_z(const dr_graph_store* store, const dr_graph
                                      int32_t z_stride, void* stream) {
   if (!z_args_ok(store, z, z_stride)) return DR_E_ARG;
   return graph_pass_launch(store, descs, n_batch, w, pass, lds_bytes, z, z_stride, stream);
+}
+
+extern "C" int64_t dr_ginet_input_grad_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t n_feat, int32_t k0,
+                                                 int32_t p1_edges, int32_t k1, int32_t transpose_aliased, int32_t out_dim,
+                                                 int32_t z_stride) {
+  if (z_stride > 0 && z_stride < (n_feat <= 32 ? 32 : 64)) return -1;
+  const int zs = z_stride > 0 ? z_stride : 0;
+  const Carve c = carve(n_nodes, n_edges, n_feat, k0, p1_edges, k1, transpose_aliased, out_dim, zs);
+  return 4LL * ig_lds(c, n_nodes, n_edges, zs).total;
+}
+
+extern "C" int dr_ginet_input_grad_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                                        const dr_ginet_weights* w, const dr_pass* pass, const dr_input_grad* ig,
+                                        const float* z, int32_t z_stride, int32_t lds_bytes, void* stream) {
+  DR_CHECK(graph_pass_check(store, descs, n_batch, w, pass, lds_bytes));
+  if (!(pass->flags & DR_PASS_BACKWARD)) return DR_E_ARG;
+  if (pass->slot || pass->step_counter) return DR_E_ARG;
+  if (!ig || !ig->dx || !ig->row_off) return DR_E_ARG;
+  if (ig->dx_stride < store->n_feat || ig->dx_stride % 4 != 0) return DR_E_ARG;
+  if (reinterpret_cast<uintptr_t>(ig->dx) % 16 != 0) return DR_E_ARG;
+  if (z && !z_args_ok(store, z, z_stride)) return DR_E_ARG;
+  if (n_batch == 0) return DR_OK;
+  if (!store->cl0 || !store->t_rowptr || !store->t_col) return DR_E_ARG;
+  GinetArgs args;
+  args.s = *store;
+  args.w = *w;
+  args.p = *pass;
+  args.descs = descs;
+  args.B = n_batch;
+  args.z = z;
+  args.z_stride = z ? z_stride : 0;
+  const dr_input_grad iga = *ig;
+#define DR_IG_LAUNCH(KPT, ZIN)                                                                                  \
+  do {                                                                                                          \
+    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_input_grad_kernel<KPT, ZIN>)));              \
+    hipLaunchKernelGGL((ginet_input_grad_kernel<KPT, ZIN>), dim3(n_batch), dim3(NT), lds_bytes,                 \
+                       (hipStream_t)stream, args, iga);                                                         \
+  } while (0)
+  if (store->n_feat <= 32) {
+    if (z) DR_IG_LAUNCH(32, true);
+    else DR_IG_LAUNCH(32, false);
+  } else {
+    if (z) DR_IG_LAUNCH(64, true);
+    else DR_IG_LAUNCH(64, false);
+  }
+#undef DR_IG_LAUNCH
+  return (int)hipGetLastError();
 }
 
 extern "C" int dr_ginet_multi_pass(const dr_graph_store* store, const dr_ginet_member* members, int32_t n_members,

@@ -238,6 +238,12 @@ class GinetMemberC(ctypes.Structure):
     _fields_ = [("w", ctypes.POINTER(GinetWeightsC)), ("pass_", ctypes.POINTER(PassC)), ("descs", VP), ("n_batch", ctypes.c_int32), ("pad", ctypes.c_int32)]
 
 
+class InputGradC(ctypes.Structure):
+    """dr_input_grad: where dr_ginet_input_grad_pass writes each graph's rows of dx."""
+
+    _fields_ = [("dx", VP), ("row_off", VP), ("dx_stride", ctypes.c_int32), ("pad0", ctypes.c_int32)]
+
+
 class ReduceMemberC(ctypes.Structure):
     """dr_reduce_member: what dr_reduce_update_opt takes, for one model of dr_reduce_multi_build."""
 
@@ -256,6 +262,8 @@ SIGNATURES = [
     ("dr_ginet_graph_pass_z", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, VP, ctypes.c_int32, VP]),
     ("dr_ginet_acc_pass_z", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, VP, _c_i32, VP, ctypes.c_int32, VP]),
     ("dr_ginet_z_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 9),
+    ("dr_ginet_input_grad_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.POINTER(InputGradC), VP, ctypes.c_int32, ctypes.c_int32, VP]),
+    ("dr_ginet_input_grad_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 9),
     ("dr_ginet_multi_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), ctypes.POINTER(GinetMemberC), ctypes.c_int32, ctypes.c_int32, VP, ctypes.c_int32, VP]),
     ("dr_reduce_multi_args_bytes", ctypes.c_int64, [ctypes.c_int32]),
     ("dr_reduce_multi_build", ctypes.c_int, [ctypes.POINTER(ReduceMemberC), ctypes.c_int32, VP, ctypes.c_int64]),

@@ -18,6 +18,8 @@
  *                           deeprank2/utils/community_pooling.py:23-27,165-242),
  *                           plus the loss gradient of Trainer._epoch
  *                           (deeprank2/trainer.py:686-689)
+ *   dr_ginet_input_grad_pass  torch.autograd.grad((model(batch) * seed).sum(), batch.x)
+ *                           on GINet (ginet.py:40-60,90-125): per-node attribution
  *   dr_fout_graph_pass      FoutNet.forward + autograd backward
  *                           (deeprank2/neuralnets/gnn/foutnet.py:48-66,99-118)
  *                           plus the same loss gradient
@@ -300,6 +302,50 @@ int dr_ginet_acc_pass_z(const dr_graph_store* store, const dr_graph_desc* descs,
 int64_t dr_ginet_z_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t n_feat, int32_t k0,
                              int32_t p1_edges, int32_t k1, int32_t transpose_aliased, int32_t out_dim,
                              int32_t z_stride);
+
+/* ---- GINet input gradients (per-node attribution) -------------------------
+ * The gradient of a GINet output with respect to the node features x
+ * (GINetConvLayer.forward ginet.py:40-60 under GINet.forward ginet.py:90-125):
+ * what
+ *   torch.autograd.grad((model(batch) * seed).sum(), batch.x)
+ * returns, in one launch.  One workgroup per graph runs dr_ginet_graph_pass's
+ * forward and backward (z == NULL; or dr_ginet_graph_pass_z's with the store's
+ * Z = A x array) -- the same arithmetic, bit for bit -- and then, from the LDS
+ * state that backward leaves (the gradient dp1 reaching each depth-0 pooling
+ * winner through relu, and the winning node a1):
+ *   dZ[i, :] = sum over (k, ch) with a1[k, ch] = i of dp1[k, ch] * [W1; W1e][ch, :F]
+ *              (channels in ascending order, one fmaf each)
+ *   dX[m, :] = sum over the transposed CSR row m (store t_rowptr / t_col: the
+ *              original edge order) of dZ[t_col[s], :], one fp32 add at a time from +0.
+ * Graph b's node m goes to dx[(row_off[b] + m) * dx_stride ...] as 16-byte rows,
+ * zeros in columns F .. dx_stride - 1.  Deterministic (no atomics); the Z and
+ * the gather form write equal bits.  The attention is identically 1 for finite
+ * inputs, so the gradient with respect to edge_attr is exactly zero and is not
+ * written.
+ * pass: what dr_ginet_graph_pass admits, with DR_PASS_BACKWARD set; normally
+ * DR_PASS_FORWARD | DR_PASS_BACKWARD with DR_LOSS_NONE and dout the seed.  A
+ * fused loss kind gives the loss's gradient with respect to x.  pass->slab and
+ * pass->head receive the training pass's partials as usual (scratch to a caller
+ * that wants dx only).  DR_E_ARG for a NULL ig, dx or row_off, a dx that is not
+ * 16-byte aligned, a dx_stride below F or not a multiple of 4, a non-NULL
+ * pass->slot or pass->step_counter, or a pass without DR_PASS_BACKWARD;
+ * DR_E_UNSUPPORTED for compute_dtype != DR_DTYPE_F32.  z, z_stride: as
+ * dr_ginet_graph_pass_z, or NULL, 0 for the gather form.  lds_bytes:
+ * dr_ginet_input_grad_lds_bytes of the batch's largest graph (z_stride 0 for
+ * the gather form: its carve holds the transposed CSR where the forward CSR
+ * was; the Z form appends it), -1 for a z_stride below the kernel's K.        */
+typedef struct dr_input_grad {
+  float* dx;               /* [rows, dx_stride] fp32, 16-byte aligned rows            */
+  const int64_t* row_off;  /* device [B]: first dx row of launch position b's graph    */
+  int32_t dx_stride;       /* multiple of 4, >= F                                      */
+  int32_t pad0;
+} dr_input_grad;
+int dr_ginet_input_grad_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                             const dr_ginet_weights* w, const dr_pass* pass, const dr_input_grad* ig,
+                             const float* z, int32_t z_stride, int32_t lds_bytes, void* stream);
+int64_t dr_ginet_input_grad_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t n_feat, int32_t k0,
+                                      int32_t p1_edges, int32_t k1, int32_t transpose_aliased, int32_t out_dim,
+                                      int32_t z_stride);
 
 /* Up to DR_MAX_MEMBERS independent GINet models (an ensemble, the folds of a
  * cross-validation, a hyper-parameter sweep) over ONE store in ONE launch:

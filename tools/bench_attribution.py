@@ -1,0 +1,152 @@
+"""Measurement: GINet input gradients (``attribution.input_gradients``), the
+fused pass against what the parent commit offers for the same numbers.
+
+configs[1]-shape synthetic graphs, one batch of B = 64.
+
+Through the public call, from the first host instruction to the device idle:
+
+* ``api_fused``      ``input_gradients(model, store, batch)``: one
+                     ``dr_ginet_input_grad_pass`` launch;
+* ``api_layers``     ``input_gradients(..., fused=False)``: ``layered.ginet_forward``
+                     with ``x`` requiring grad, then ``torch.autograd.grad`` — the
+                     only route to these numbers at the parent: the baseline.
+
+With everything a caller can keep between batches kept (the handle, the batch
+tensors and their pooling plan, the buffers):
+
+* ``launch_ig``      the bare ``dr_ginet_input_grad_pass`` launch;
+* ``launch_pass_z``  ``dr_ginet_graph_pass_z`` with FORWARD | BACKWARD on the same
+                     batch: the difference prices the epilogue (dZ, dX = A^T dZ);
+* ``layers_steady``  the layer route's forward + ``autograd.grad`` alone.
+
+Wall-clock us per batch (``--reps`` calls per timing, the device idle before
+and after).  The variants are interleaved in one process and each runs
+``--runs`` times; the table gives the mean and the spread (max - min).  The
+last lines say whether the fused route beats the layer route by more than five
+times that route's own spread (the bar for keeping it the default).
+"""
+
+from __future__ import annotations
+
+import argparse
+import copy
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "deeprank-gnn-2_amd")]
+
+from bench import make_graphs, records  # noqa: E402
+from deeprank2_amd import _lib, attribution, layered  # noqa: E402
+from deeprank2_amd.fused import BatchHandle, make_pass, z_lds_for  # noqa: E402
+from deeprank2_amd.neuralnets.gnn import ginet  # noqa: E402
+from deeprank2_amd.store import GraphStore, pack_graphs  # noqa: E402
+
+B = 64
+
+
+def wall_us(body, reps):
+    """us per call of ``reps`` calls of ``body``, the device idle before and after."""
+    body()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        body()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e6 / reps
+
+
+def interleaved(variants, runs, reps):
+    times = {name: [] for name in variants}
+    for _ in range(runs):
+        for name, body in variants.items():
+            times[name].append(wall_us(body, reps))
+    return times
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--reps", type=int, default=200, help="calls per timing (200: the layer route's timing window is over a second)")
+    ap.add_argument("--runs", type=int, default=3)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    store = GraphStore(pack_graphs(records(make_graphs("residue", B, 1000))), dev)
+    torch.manual_seed(0)
+    model = ginet.GINet(30, 1, 3).to(dev).eval()
+    idx = np.arange(B)
+    f, xs, out_dim = store.n_feat, store.x_stride, 1
+
+    def api_fused():
+        return attribution.input_gradients(model, store, indices=idx, batch_size=B, fused=True)
+
+    def api_layers():
+        return attribution.input_gradients(model, store, indices=idx, batch_size=B, fused=False)
+
+    a, b = api_fused(), api_layers()
+    assert a.path == "fused" and b.path == "layers"
+    scale = float(b.dx.abs().max())
+    assert torch.allclose(a.dx, b.dx, rtol=1e-4, atol=1e-6 * scale) and torch.allclose(a.out, b.out, rtol=1e-4, atol=1e-4), "the two routes agree"
+
+    # the kept state of the bare launches
+    h = BatchHandle(store, idx.astype(np.int32))
+    params = [p.detach().contiguous() for p in model.ordered_params()]
+    w = ginet.weights_c(params)
+    z, zs = store.agg_x(), store.agg_x_stride
+    seed = torch.ones(B, out_dim, device=dev)
+    out = torch.empty(B, out_dim, device=dev)
+    slab = torch.empty(B * ginet.slab_stride(f), device=dev)
+    head = torch.zeros(B * ginet.head_stride(out_dim), device=dev)
+    p = make_pass(out_dim, _lib.DR_PASS_FORWARD | _lib.DR_PASS_BACKWARD, dout=seed, out=out, slab=slab, head=head)
+    dx = torch.empty(int(a.node_off[-1]), xs, device=dev)
+    row_off = torch.from_numpy(a.node_off[:-1].copy()).to(dev)
+    ig = _lib.InputGradC()
+    ig.dx, ig.row_off, ig.dx_stride = dx.data_ptr(), row_off.data_ptr(), xs
+    lib = _lib.load()
+    alias = int(store.packed.transpose_aliased)
+    lds_ig = int(lib.dr_ginet_input_grad_lds_bytes(*h.max_sizes[:2], f, *h.max_sizes[2:], alias, out_dim, zs))
+    lds_z = z_lds_for(h, out_dim)
+    stream = _lib.stream_ptr(dev)
+
+    def launch_ig():
+        _lib.check(lib.dr_ginet_input_grad_pass(store.cstruct(), h.descs.data_ptr(), B, w, p, ig, z.data_ptr(), zs, lds_ig, stream), "dr_ginet_input_grad_pass")
+
+    def launch_pass_z():
+        _lib.check(lib.dr_ginet_graph_pass_z(store.cstruct(), h.descs.data_ptr(), B, w, p, lds_z, z.data_ptr(), zs, stream), "dr_ginet_graph_pass_z")
+
+    t = copy.copy(layered.batch_tensors(h))
+    t.x = t.x.detach().clone().requires_grad_(True)
+
+    def layers_steady():
+        o = layered.ginet_forward(model, t, training=False)
+        return torch.autograd.grad((o * seed).sum(), t.x)
+
+    launch_ig()
+    torch.cuda.synchronize()
+    assert torch.equal(dx[:, :f], a.dx), "the bare launch writes the public call's bits"
+
+    times = interleaved({"api_fused": api_fused, "api_layers": api_layers, "launch_ig": launch_ig, "launch_pass_z": launch_pass_z, "layers_steady": layers_steady}, args.runs, args.reps)
+    rows = []
+    print(f"{'variant':>14} {'us/batch':>10} {'spread us':>10}  runs")
+    for name, ts in times.items():
+        mean, spread = float(np.mean(ts)), float(max(ts) - min(ts))
+        rows.append({"variant": name, "us": round(mean, 2), "spread_us": round(spread, 2), "runs_us": [round(x, 2) for x in ts]})
+        print(f"{name:>14} {mean:10.1f} {spread:10.1f}  {' '.join(f'{x:.1f}' for x in ts)}")
+    verdicts = []
+    for new, old in (("api_fused", "api_layers"), ("launch_ig", "layers_steady")):
+        n_, o_ = times[new], times[old]
+        margin = 5 * (max(o_) - min(o_))
+        wins = bool(np.mean(o_) - np.mean(n_) > margin)
+        verdicts.append({"fused": new, "baseline": old, "fused_us": round(float(np.mean(n_)), 2), "baseline_us": round(float(np.mean(o_)), 2), "five_spreads_us": round(margin, 2), "fused_wins": wins})
+        print(f"{new} {np.mean(n_):.1f} us against {old} {np.mean(o_):.1f} us, 5 x the baseline's spread {margin:.1f} us -> {'fused wins' if wins else 'no win'}")
+    epi = float(np.mean(times["launch_ig"]) - np.mean(times["launch_pass_z"]))
+    print(f"epilogue (launch_ig - launch_pass_z): {epi:.2f} us per batch")
+    print(json.dumps({"bench": "attribution", "B": B, "reps": args.reps, "runs": args.runs, "rows": rows, "verdicts": verdicts, "epilogue_us": round(epi, 2)}))
+
+
+if __name__ == "__main__":
+    main()
