@@ -52,6 +52,19 @@ inline int dr_check_loss(const dr_pass* p) {
   }
 }
 
+// Host: the pointers a pass's flags ask for and its dropout mode (every
+// graph-pass entry, after its own shape and LDS checks).  has_dropout: the
+// family's head has dropout (GINet); the others run with DR_DROPOUT_OFF only.
+inline int dr_check_pass_args(const dr_pass* p, bool has_dropout) {
+  if ((p->flags & DR_PASS_BACKWARD) && (!p->slab || !p->head)) return DR_E_ARG;
+  if ((p->flags & DR_PASS_BACKWARD) && p->loss_kind == DR_LOSS_NONE && !p->dout) return DR_E_ARG;
+  if ((p->flags & DR_PASS_FORWARD) && !p->out) return DR_E_ARG;
+  if (!has_dropout) return p->use_dropout != DR_DROPOUT_OFF ? DR_E_UNSUPPORTED : DR_OK;
+  if (p->use_dropout == DR_DROPOUT_MASK && !p->mask) return DR_E_ARG;
+  if (p->use_dropout < DR_DROPOUT_OFF || p->use_dropout > DR_DROPOUT_HASH) return DR_E_ARG;
+  return DR_OK;
+}
+
 // Sum over the 64 lanes of a wave (butterfly; every lane gets the total).
 __device__ __forceinline__ float dr_wave_sum(float v) {
 #pragma unroll

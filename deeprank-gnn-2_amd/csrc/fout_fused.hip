@@ -33,16 +33,6 @@
 
 #include "graph_common.h"
 
-#ifndef DR_FOUT_FRONT
-#define DR_FOUT_FRONT 1  // FoutNet per-graph kernel: Zm, conv1 and depth-0 pooling fused per wave (0: three barrier phases)
-#endif
-#ifndef DR_FOUT_MSE_HEAD
-#define DR_FOUT_MSE_HEAD 1  // FoutNet tail: one MSE logit's logit / loss / dh on wave 0 without barriers (0: the general head)
-#endif
-#ifndef DR_TILE_STORE_WAIT
-#define DR_TILE_STORE_WAIT 0  // 1: the tile kernel waits for its Zm stores before the MFMA phase (r05 form, A/B)
-#endif
-
 namespace {
 
 using namespace drk;
@@ -166,7 +156,6 @@ __device__ __forceinline__ float4 gather_row_chunk_w(const uint16_t* col, const 
 // together; the fmaf chain and the weight sum in edge order as above
 __device__ __forceinline__ float4 gather_row_chunk_w_lds(const uint16_t* col, const float* w, int eb, int ee,
                                                          const float* X, int XS, int c4, float& sw) {
-#if DR_GATHER_IMM
   const char* xc = reinterpret_cast<const char*>(X + c4);
   const int rb = XS * 4;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -196,9 +185,6 @@ __device__ __forceinline__ float4 gather_row_chunk_w_lds(const uint16_t* col, co
   }
   sw = s;
   return acc;
-#else
-  return gather_row_chunk_w(col, w, eb, ee, X, XS, c4, sw);
-#endif
 }
 
 // gather_row_chunk_w_lds for two 16-byte chunks of a row at once (the fused
@@ -345,7 +331,7 @@ __device__ __forceinline__ void fout_tail(const dr_pass& p, const FoutTail t, in
     }
   }
   __syncthreads();
-  if (DR_FOUT_MSE_HEAD && OUT == 1 && p.loss_kind == DR_LOSS_MSE && (p.flags & DR_PASS_BACKWARD)) {
+  if (OUT == 1 && p.loss_kind == DR_LOSS_MSE && (p.flags & DR_PASS_BACKWARD)) {
     // one MSE logit (configs[2]): wave 0 forms the logit (the same wave sum),
     // the loss gradient and dh for the 64 hidden units, with no workgroup
     // barrier between them (as ginet_head.h's MSE path)
@@ -589,37 +575,37 @@ __global__ void __launch_bounds__(NT) fout_graph_kernel(FoutArgs a) {
   const float y_g = s.y[g];
   // no dropout here, but the step counter contract holds: snapshot for
   // dr_reduce_update (stored after the staging wait below)
-  dma_x4<NT>(sX, s.x + n0 * (int64_t)XS, N * XS / 4);
-  dma_x4<NT>(scol, s.col + ec0, (E + 7) / 8);
-  dma_words<NT>(srp, s.rowptr + n0 + g, N + 1);
-  dma_words<NT>(sm0p, s.m0_ptr + k00 + g, K0 + 1);
-  dma_words<NT>(sm0i, s.m0_idx + n0, N);
-  dma_words<NT>(sp1rp, s.p1_rowptr + k00 + g, K0 + 1);
-  dma_words<NT>(sp1c, s.p1_col + q0, P1);
+  dma_copy<NT, 16>(sX, s.x + n0 * (int64_t)XS, N * XS / 4);
+  dma_copy<NT, 16>(scol, s.col + ec0, (E + 7) / 8);
+  dma_copy<NT, 4>(srp, s.rowptr + n0 + g, N + 1);
+  dma_copy<NT, 4>(sm0p, s.m0_ptr + k00 + g, K0 + 1);
+  dma_copy<NT, 4>(sm0i, s.m0_idx + n0, N);
+  dma_copy<NT, 4>(sp1rp, s.p1_rowptr + k00 + g, K0 + 1);
+  dma_copy<NT, 4>(sp1c, s.p1_col + q0, P1);
   if (!alias) {
-    dma_words<NT>(sp1trp, s.p1t_rowptr + k00 + g, K0 + 1);
-    dma_words<NT>(sp1tc, s.p1t_col + q0, P1);
+    dma_copy<NT, 4>(sp1trp, s.p1t_rowptr + k00 + g, K0 + 1);
+    dma_copy<NT, 4>(sp1tc, s.p1t_col + q0, P1);
   }
-  dma_words<NT>(sm1p, s.m1_ptr + k10 + g, K1 + 1);
-  dma_words<NT>(sm1i, s.m1_idx + k00, K0);
+  dma_copy<NT, 4>(sm1p, s.m1_ptr + k10 + g, K1 + 1);
+  dma_copy<NT, 4>(sm1i, s.m1_idx + k00, K0);
   if (SG) {  // Fe == 1: edge weights are contiguous at col_off, pooled ones at p1_off
-    dma_words<NT>(sEa, s.ea + ec0, E);
-    dma_words<NT>(sP1w, s.p1_ea + q0, P1);
-    dma_words<NT>(sP1tid, s.p1t_pid + q0, P1);
+    dma_copy<NT, 4>(sEa, s.ea + ec0, E);
+    dma_copy<NT, 4>(sP1w, s.p1_ea + q0, P1);
+    dma_copy<NT, 4>(sP1tid, s.p1t_pid + q0, P1);
   }
   // The fused front (FoutNet, F <= 32, K0 <= 64): each wave gathers its 16-row
   // tile's Zm, runs conv1 on it and pools it by 64-bit LDS atomic max keys
   // (ginet_fused.hip's front half), so conv1's weights and the node clusters
   // are staged here, the keys live in the reduction scratch and the H1 rows
   // are never formed (the tail reads P1 / A1 and [x | Zm] at the args only).
-  const bool FRONT = DR_FOUT_FRONT && XS <= 32 && K0 * 32 <= 2 * NT;
+  const bool FRONT = XS <= 32 && K0 * 32 <= 2 * NT;
   int* scl0 = reinterpret_cast<int*>(sH1);
   unsigned long long* skey = reinterpret_cast<unsigned long long*>(sRed);
   if (FRONT) {
-    dma_words<NT>(scl0, s.cl0 + n0, N);
-    dma_words<NT>(sWc1, a.w.wc1, F * 16);  // [Wc; Wn] k-major, as the weight image below
-    dma_words<NT>(sWc1 + F * 16, a.w.wn1, F * 16);
-    dma_words<NT>(sB1, a.w.b1, 16);
+    dma_copy<NT, 4>(scl0, s.cl0 + n0, N);
+    dma_copy<NT, 4>(sWc1, a.w.wc1, F * 16);  // [Wc; Wn] k-major, as the weight image below
+    dma_copy<NT, 4>(sWc1 + F * 16, a.w.wn1, F * 16);
+    dma_copy<NT, 4>(sB1, a.w.b1, 16);
     for (int p = 2 * F * 16 + tid; p < KP * 16; p += NT) sWc1[p] = 0.f;  // K padding rows
     for (int p = tid; p < K0 * 16; p += NT) skey[p] = 0ull;
   }
@@ -953,17 +939,15 @@ __global__ void __launch_bounds__(NTA) fout_large_conv1_kernel(FoutLargeArgs la)
   int* sm0p = reinterpret_cast<int*>(lds + c.m0p);
   // Zm (and SGAT's c1) go to global memory only at the tile's depth-0 pooling
   // arg candidates: the tail reads them only at the final args, tile args
-  constexpr bool ZARGS = DR_Z_ARGS;
   int* sflag = reinterpret_cast<int*>(lds + c.flg);
-  if (ZARGS)
-    for (int p = tid; p < TRr; p += NTA) sflag[p] = 0;
+  for (int p = tid; p < TRr; p += NTA) sflag[p] = 0;
   const bool compact = pl.tile_members != nullptr;
   if (compact) {  // this tile's members by cluster (host-built), runs from tile_mptr
-    dma_words<NTA>(sm0i, pl.tile_members + (int64_t)tile * TRr, nrows);
-    dma_words<NTA>(sm0p, pl.tile_mptr + (int64_t)tile * (pl.k0_max + 1), K0 + 1);
+    dma_copy<NTA, 4>(sm0i, pl.tile_members + (int64_t)tile * TRr, nrows);
+    dma_copy<NTA, 4>(sm0p, pl.tile_mptr + (int64_t)tile * (pl.k0_max + 1), K0 + 1);
   } else {
-    dma_words<NTA>(sm0i, s.m0_idx + n0, N);
-    dma_words<NTA>(sm0p, s.m0_ptr + k00 + g, K0 + 1);
+    dma_copy<NTA, 4>(sm0i, s.m0_idx + n0, N);
+    dma_copy<NTA, 4>(sm0p, s.m0_ptr + k00 + g, K0 + 1);
   }
   for (int p = tid; p < KP * 16; p += NTA) {  // [Wc; Wn; 0], k-major as stored
     const int k = p >> 4, o = p & 15;
@@ -993,11 +977,7 @@ __global__ void __launch_bounds__(NTA) fout_large_conv1_kernel(FoutLargeArgs la)
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           if (c4 + q < F) sA[r * LDA + F + c4 + q] = zv[q];
-        if (!ZARGS) *reinterpret_cast<float4*>(zg + (int64_t)(r0 + r) * ZS + c4) = zm;
-        if (SG && ch == 0) {
-          sC1[r] = sw / deg;
-          if (!ZARGS) zg[(int64_t)(r0 + r) * ZS + XS] = sw / deg;
-        }
+        if (SG && ch == 0) sC1[r] = sw / deg;
       }
     }
   };
@@ -1008,14 +988,14 @@ __global__ void __launch_bounds__(NTA) fout_large_conv1_kernel(FoutLargeArgs la)
     float* sXh = lds + c.xh;
     float* sEw;
     const int h0 = pl.halo_off[tile], H = pl.halo_off[tile + 1] - h0;
-    dma_words<NTA>(strp, s.rowptr + n0 + g + r0, nrows + 1);
-    dma_words<NTA>(shid, pl.halo_ids + h0, H);
+    dma_copy<NTA, 4>(strp, s.rowptr + n0 + g + r0, nrows + 1);
+    dma_copy<NTA, 4>(shid, pl.halo_ids + h0, H);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     const int ebase = strp[0], ne = strp[nrows] - ebase;
     sEw = lds + c.lcol + r4((ne + 8) / 2);
-    dma_x4<NTA>(slcol, pl.lcol + pl.lcol_off[tile], (ne + 7) / 8);
-    if (SG) dma_words<NTA>(sEw, s.ea + ec0 + ebase, ne);  // Fe == 1: weights contiguous in CSR order
+    dma_copy<NTA, 16>(slcol, pl.lcol + pl.lcol_off[tile], (ne + 7) / 8);
+    if (SG) dma_copy<NTA, 4>(sEw, s.ea + ec0 + ebase, ne);  // Fe == 1: weights contiguous in CSR order
     {
       const int nch = XS >> 2, tot = H * nch;
       const int wv = __builtin_amdgcn_readfirstlane(wave);
@@ -1032,7 +1012,6 @@ __global__ void __launch_bounds__(NTA) fout_large_conv1_kernel(FoutLargeArgs la)
     gather_rows(s.col + ec0, SG ? s.ea + ec0 : nullptr, X, s.rowptr + n0 + g + r0, 0);
   }
   // (no wait for the Zm stores: the MFMA reads LDS; the tail reads Zm next launch)
-  if (DR_TILE_STORE_WAIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   // conv1 on MFMA: H1 = relu([c1 x | Zm] [Wc; Wn] + b) -- fout_graph_kernel's operand order
   {
@@ -1091,23 +1070,22 @@ __global__ void __launch_bounds__(NTA) fout_large_conv1_kernel(FoutLargeArgs la)
         arg = i;
       }
     }
-    if (ZARGS && arg < N) sflag[arg - r0] = 1;  // (benign race: every writer stores 1)
+    if (arg < N) sflag[arg - r0] = 1;  // (benign race: every writer stores 1)
     if (best > LOWEST)
       __hip_atomic_fetch_max((__attribute__((address_space(1))) unsigned long long*)(pl.part_key) + ((int64_t)b * pl.k0_max + k) * 32 + ch,
                              ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)arg),
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (ZARGS) {  // the flagged rows' Zm (from the A tile's columns F..2F-1) and c1
-    __syncthreads();
-    const int nch = XS >> 2;
-    for (int p = tid; p < nrows * nch; p += NTA) {
-      const int r = p / nch, c4 = (p - r * nch) * 4;
-      if (sflag[r]) {
-        const float* zr = sA + r * LDA + F + c4;
-        *reinterpret_cast<float4*>(zg + (int64_t)(r0 + r) * ZS + c4) =
-            make_float4(zr[0], c4 + 1 < F ? zr[1] : 0.f, c4 + 2 < F ? zr[2] : 0.f, c4 + 3 < F ? zr[3] : 0.f);
-        if (SG && c4 == 0) zg[(int64_t)(r0 + r) * ZS + XS] = sC1[r];
-      }
+  // the flagged rows' Zm (from the A tile's columns F..2F-1) and c1
+  __syncthreads();
+  const int nch = XS >> 2;
+  for (int p = tid; p < nrows * nch; p += NTA) {
+    const int r = p / nch, c4 = (p - r * nch) * 4;
+    if (sflag[r]) {
+      const float* zr = sA + r * LDA + F + c4;
+      *reinterpret_cast<float4*>(zg + (int64_t)(r0 + r) * ZS + c4) =
+          make_float4(zr[0], c4 + 1 < F ? zr[1] : 0.f, c4 + 2 < F ? zr[2] : 0.f, c4 + 3 < F ? zr[3] : 0.f);
+      if (SG && c4 == 0) zg[(int64_t)(r0 + r) * ZS + XS] = sC1[r];
     }
   }
 }
@@ -1204,17 +1182,17 @@ __global__ void __launch_bounds__(NT) fout_large_tail_kernel(FoutLargeArgs la) {
   t.P1tid = reinterpret_cast<int*>(lds + c.p1tid);
   t.C2 = lds + c.c2;
   const float y_g = s.y[g];
-  dma_words<NT>(t.p1rp, s.p1_rowptr + k00 + g, K0 + 1);
-  dma_words<NT>(t.p1c, s.p1_col + q0, P1);
+  dma_copy<NT, 4>(t.p1rp, s.p1_rowptr + k00 + g, K0 + 1);
+  dma_copy<NT, 4>(t.p1c, s.p1_col + q0, P1);
   if (!alias) {
-    dma_words<NT>(t.p1trp, s.p1t_rowptr + k00 + g, K0 + 1);
-    dma_words<NT>(t.p1tc, s.p1t_col + q0, P1);
+    dma_copy<NT, 4>(t.p1trp, s.p1t_rowptr + k00 + g, K0 + 1);
+    dma_copy<NT, 4>(t.p1tc, s.p1t_col + q0, P1);
   }
-  dma_words<NT>(t.m1p, s.m1_ptr + k10 + g, K1 + 1);
-  dma_words<NT>(t.m1i, s.m1_idx + k00, K0);
+  dma_copy<NT, 4>(t.m1p, s.m1_ptr + k10 + g, K1 + 1);
+  dma_copy<NT, 4>(t.m1i, s.m1_idx + k00, K0);
   if (SG) {
-    dma_words<NT>(t.P1w, s.p1_ea + q0, P1);
-    dma_words<NT>(t.P1tid, s.p1t_pid + q0, P1);
+    dma_copy<NT, 4>(t.P1w, s.p1_ea + q0, P1);
+    dma_copy<NT, 4>(t.P1tid, s.p1t_pid + q0, P1);
   }
   for (int p = tid; p < 1072; p += NT) {
     const int q = p;
@@ -1252,10 +1230,7 @@ int fout_family_pass(bool sg, const dr_graph_store* store, const dr_graph_desc* 
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
   if (store->n_feat < 1 || 2 * 16 * store->n_feat + 1072 + 2112 + 65 * pass->out_dim > 6 * NT) return DR_E_UNSUPPORTED;
   if (lds_bytes > 160 * 1024) return DR_E_LDS;
-  if ((pass->flags & DR_PASS_BACKWARD) && (!pass->slab || !pass->head)) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_BACKWARD) && pass->loss_kind == DR_LOSS_NONE && !pass->dout) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_FORWARD) && !pass->out) return DR_E_ARG;
-  if (pass->use_dropout != DR_DROPOUT_OFF) return DR_E_UNSUPPORTED;  // FoutNet / SGAT have no dropout
+  DR_CHECK(dr_check_pass_args(pass, false));  // FoutNet / SGAT have no dropout
   if (n_batch == 0) return DR_OK;
   const void* fn = sg ? reinterpret_cast<const void*>(&fout_graph_kernel<true>)
                       : reinterpret_cast<const void*>(&fout_graph_kernel<false>);
@@ -1325,10 +1300,8 @@ int fout_large_family(bool sg, const dr_graph_store* store, const dr_graph_desc*
                          !plan->lcol || !plan->tile_members || !plan->tile_mptr))
     return DR_E_ARG;
   if (!plan->halo_ids && plan->halo_max) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_BACKWARD) && (!pass->slab || !pass->head)) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_BACKWARD) && pass->loss_kind == DR_LOSS_NONE && !pass->dout) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_FORWARD) && !pass->out) return DR_E_ARG;
-  if (pass->use_dropout != DR_DROPOUT_OFF || pass->compute_dtype != DR_DTYPE_F32) return DR_E_UNSUPPORTED;
+  DR_CHECK(dr_check_pass_args(pass, false));
+  if (pass->compute_dtype != DR_DTYPE_F32) return DR_E_UNSUPPORTED;
   if (n_batch == 0) return DR_OK;
   const void* conv = sg ? reinterpret_cast<const void*>(&fout_large_conv1_kernel<true>) : reinterpret_cast<const void*>(&fout_large_conv1_kernel<false>);
   const void* tail = sg ? reinterpret_cast<const void*>(&fout_large_tail_kernel<true>) : reinterpret_cast<const void*>(&fout_large_tail_kernel<false>);

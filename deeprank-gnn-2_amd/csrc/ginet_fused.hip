@@ -37,6 +37,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/deeprank2_amd.h"
 #include "dr_common.h"
@@ -45,41 +46,85 @@
 
 namespace {
 
-#ifndef DR_GATHER_ROW2
-#define DR_GATHER_ROW2 1  // GINet gather: one row, two chunks per lane (0: two rows, one chunk)
-#endif
-#ifndef DR_CONV2_KEYS
-#define DR_CONV2_KEYS 0  // 1: conv2 reads the pooled rows from the depth-0 keys, no barrier after their decode (measured 0.1 us slower, r05)
-#endif
-#ifndef DR_TILE_STORE_WAIT
-#define DR_TILE_STORE_WAIT 0  // 1: the tile kernels wait for their Z stores before the MFMA phase (r05 form, A/B)
-#endif
-#ifndef DR_ZIN_EARLY_W
-#define DR_ZIN_EARLY_W 1  // Z-input kernels: conv2 / head weights requested with the staging DMA (0: after the staging barrier, as the gather kernels; A/B)
-#endif
-#ifndef DR_W1_IMAGE
-#define DR_W1_IMAGE 1  // KPT = 32: conv1's B operands staged as a lane-ordered image and read 16 bytes at a time (0: row-major [W1; W1e], 4-byte reads; A/B)
-#endif
-#ifndef DR_DMA_ROT
-#define DR_DMA_ROT 0  // 1: spread starting waves (measured 0.1 us slower per pass, r05)
-#endif
+using namespace drk;
+
 constexpr int NT = 1024;     // 16 waves
 constexpr int NW = NT / 64;
 constexpr int HEADW = 672;   // G64 hpre128 hh128 hd128 dh128 dG64 dout16 spare16
-constexpr float LOWEST = -3.402823466e+38f;
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) unsigned long long gu64;
-typedef __attribute__((address_space(1))) unsigned int gu32;
-
-__host__ __device__ inline int r4(int v) { return (v + 3) & ~3; }
-__host__ __device__ inline int r16(int v) { return (v + 15) & ~15; }
 
 struct Carve {
   int KP, LDW, XS;
   int w1, w2, fc2, x, z, rp, col, cl0, key, p1, a1, dp1, y2, h2, p1rp, p1c, p1trp, p1tc, m1p, m1i, p2, nt, cl1,
       head, dgp, keep, total;
 };
+
+// A walk over LDS in 4-byte words: each region starts 16-byte aligned.
+struct LdsWalk {
+  int o = 0;
+  __host__ __device__ __forceinline__ void take(int& field, int words) {
+    field = o;
+    o += r4(words);
+  }
+};
+
+// The regions every GINet carve lists, each written once (C: Carve or TailCarve).
+template <class C>
+__host__ __device__ __forceinline__ void take_head_weights(C& c, LdsWalk& w, int OUT) {
+  w.take(c.w2, 1024);             // [W2 | W2e] (conv2 / conv2_ext .fc.weight)
+  w.take(c.fc2, OUT * 128 + OUT); // fc2.weight rows, then fc2.bias
+}
+// the pooled graph and its transpose (one copy where the store aliases them), then the depth-1 members
+template <class C>
+__host__ __device__ __forceinline__ void take_pooled_inputs(C& c, LdsWalk& w, int K0, int P1, int K1, int alias) {
+  w.take(c.p1rp, K0 + 1);
+  w.take(c.p1c, P1);
+  if (alias) {
+    c.p1trp = c.p1rp;
+    c.p1tc = c.p1c;
+  } else {
+    w.take(c.p1trp, K0 + 1);
+    w.take(c.p1tc, P1);
+  }
+  w.take(c.m1p, K1 + 1);
+  w.take(c.m1i, K0);
+}
+template <class C>
+__host__ __device__ __forceinline__ void take_pool0(C& c, LdsWalk& w, int K0) {
+  w.take(c.p1, K0 * 32);
+  w.take(c.a1, K0 * 32);
+  w.take(c.dp1, K0 * 32);
+  w.take(c.y2, K0 * 64);
+  w.take(c.h2, K0 * 64);
+}
+template <class C>
+__host__ __device__ __forceinline__ void take_pool1_head(C& c, LdsWalk& w, int K0, int K1) {
+  w.take(c.p2, K1 * 64);
+  w.take(c.nt, K1 * 64);
+  w.take(c.cl1, K0);  // depth-1 cluster of each depth-0 cluster
+  w.take(c.head, HEADW);
+  w.take(c.dgp, NW * 64);
+}
+// The sixteen regions from p1 to dgp, in the order carve() and tail_carve()
+// share (everything the tail works in but the conv2 / head weights).
+template <class C>
+__host__ __device__ __forceinline__ void take_tail_regions(C& c, LdsWalk& w, int K0, int P1, int K1, int alias) {
+  take_pool0(c, w, K0);
+  take_pooled_inputs(c, w, K0, P1, K1, alias);
+  take_pool1_head(c, w, K0, K1);
+}
+
+// K padded to the kernel's KPT (32 for F <= 32, else 64: the MFMA steps it
+// runs; zeros past F).  (Until r05 KP was r16(F), shorter than KPT for F <= 16
+// and 33..48: the padding zeroed to KPT then ran 14 words past Z into the
+// row pointers being DMA'd beside it, and the last k steps read other
+// waves' rows.)
+__host__ __device__ __forceinline__ void carve_strides(Carve& c, int F, int zs) {
+  c.KP = F <= 32 ? 32 : 64;
+  c.LDW = zs > 0 ? zs : c.KP + 2;  // rows 2 words apart: lanes (row li, k+kq) hit 32 distinct banks
+  c.XS = r4(F);
+  c.x = c.rp = c.col = 0;
+}
 
 // LDS carve (4-byte words, every region 16-byte aligned).  X keeps the HBM
 // row stride XS = r4(F) (16-byte rows for the DMA and the float4 gather);
@@ -88,58 +133,23 @@ struct Carve {
 // zs > 0: the Z-input form (dr_ginet_graph_pass_z): Z = A·X arrives from the
 // store's array with rows of zs words, the stride it keeps in LDS, and the X,
 // row pointer and column regions go.
-__host__ __device__ inline Carve carve(int N, int E, int F, int K0, int P1, int K1, int alias, int OUT, int zs = 0) {
+__host__ __device__ __forceinline__ Carve carve(int N, int E, int F, int K0, int P1, int K1, int alias, int OUT, int zs = 0) {
   Carve c;
-  // K padded to the kernel's KPT (32 for F <= 32, else 64: the MFMA steps it
-  // runs; zeros past F).  (Until r05 KP was r16(F), shorter than KPT for F <= 16
-  // and 33..48: the padding zeroed to KPT then ran 14 words past Z into the
-  // row pointers being DMA'd beside it, and the last k steps read other
-  // waves' rows.)
-  c.KP = F <= 32 ? 32 : 64;
-  c.LDW = zs > 0 ? zs : c.KP + 2;   // rows 2 words apart: lanes (row li, k+kq) hit 32 distinct banks
-  c.XS = r4(F);
-  c.x = c.rp = c.col = 0;
-  int o = 0;
-#define TAKE(field, words) \
-  {                        \
-    c.field = o;           \
-    o += r4(words);        \
-  }
-  TAKE(w1, 32 * F)           // [W1; W1e] (conv1 / conv1_ext .fc.weight), rows of F
-  TAKE(w2, 1024)             // [W2 | W2e] (conv2 / conv2_ext .fc.weight)
-  TAKE(fc2, OUT * 128 + OUT) // fc2.weight rows, then fc2.bias
-  if (zs <= 0) TAKE(x, N * c.XS)
-  TAKE(z, N * c.LDW)
+  carve_strides(c, F, zs);
+  LdsWalk w;
+  w.take(c.w1, 32 * F);  // [W1; W1e] (conv1 / conv1_ext .fc.weight), rows of F
+  take_head_weights(c, w, OUT);
+  if (zs <= 0) w.take(c.x, N * c.XS);
+  w.take(c.z, N * c.LDW);
   if (zs <= 0) {
-    TAKE(rp, N + 1)
-    TAKE(col, (E + 1) / 2)   // uint16 column ids
+    w.take(c.rp, N + 1);
+    w.take(c.col, (E + 1) / 2);  // uint16 column ids
   }
-  TAKE(cl0, N)               // depth-0 cluster of each node
-  TAKE(key, 2 * K0 * 32)     // depth-0 pooling keys (uint64)
-  TAKE(p1, K0 * 32)
-  TAKE(a1, K0 * 32)
-  TAKE(dp1, K0 * 32)
-  TAKE(y2, K0 * 64)
-  TAKE(h2, K0 * 64)
-  TAKE(p1rp, K0 + 1)
-  TAKE(p1c, P1)
-  if (alias) {
-    c.p1trp = c.p1rp;
-    c.p1tc = c.p1c;
-  } else {
-    TAKE(p1trp, K0 + 1)
-    TAKE(p1tc, P1)
-  }
-  TAKE(m1p, K1 + 1)
-  TAKE(m1i, K0)
-  TAKE(p2, K1 * 64)
-  TAKE(nt, K1 * 64)
-  TAKE(cl1, K0)  // depth-1 cluster of each depth-0 cluster
-  TAKE(head, HEADW)
-  TAKE(dgp, NW * 64)
-  TAKE(keep, 32)  // 128 dropout keep bytes
-#undef TAKE
-  c.total = o;
+  w.take(c.cl0, N);             // depth-0 cluster of each node
+  w.take(c.key, 2 * K0 * 32);   // depth-0 pooling keys (uint64)
+  take_tail_regions(c, w, K0, P1, K1, alias);
+  w.take(c.keep, 32);  // 128 dropout keep bytes
+  c.total = w.o;
   return c;
 }
 
@@ -151,77 +161,66 @@ __host__ __device__ inline Carve carve(int N, int E, int F, int K0, int P1, int 
 //   m1i] [inputs, parity 1] [scratch: z key p1 a1 dp1 y2 h2 p2 nt cl1 head
 //   dgp keep]
 // (word offsets from the carve base; each region sized for the batch maxima).
+// Three segments, each a walk of its own: a graph's carve (carve_acc) places
+// them at the layout's segment starts, and the layout (acc_layout) is the
+// same walks run on the batch maxima.
 struct AccLayout {
   int in0, in1, scr, total;
 };
 
-__host__ __device__ inline Carve carve_acc(int N, int E, int F, int K0, int P1, int K1, int alias, int OUT,
+__host__ __device__ __forceinline__ void acc_take_weights(Carve& c, LdsWalk& w, int F, int OUT) {
+  w.take(c.w1, 32 * F);
+  take_head_weights(c, w, OUT);
+}
+__host__ __device__ __forceinline__ void acc_take_inputs(Carve& c, LdsWalk& w, int N, int E, int K0, int P1, int K1, int alias,
+                                                int zs) {
+  if (zs > 0) {  // Z is an input: one copy per parity, the next graph's DMA'd under this graph's tail
+    w.take(c.z, N * c.LDW);
+  } else {
+    w.take(c.x, N * c.XS);
+    w.take(c.rp, N + 1);
+    w.take(c.col, (E + 1) / 2);
+  }
+  w.take(c.cl0, N);
+  take_pooled_inputs(c, w, K0, P1, K1, alias);
+}
+__host__ __device__ __forceinline__ void acc_take_scratch(Carve& c, LdsWalk& w, int N, int K0, int K1, int zs) {
+  if (zs <= 0) w.take(c.z, N * c.LDW);
+  w.take(c.key, 2 * K0 * 32);
+  take_pool0(c, w, K0);
+  take_pool1_head(c, w, K0, K1);
+  w.take(c.keep, 32);
+}
+
+__host__ __device__ __forceinline__ Carve carve_acc(int N, int E, int F, int K0, int P1, int K1, int alias, int OUT,
                                            const AccLayout& L, int par, int zs = 0) {
   Carve c;
-  c.KP = F <= 32 ? 32 : 64;  // as carve()
-  c.LDW = zs > 0 ? zs : c.KP + 2;
-  c.XS = r4(F);
-  c.x = c.rp = c.col = 0;
-  int o = 0;
-#define TAKE(field, words) \
-  {                        \
-    c.field = o;           \
-    o += r4(words);        \
-  }
-  TAKE(w1, 32 * F)
-  TAKE(w2, 1024)
-  TAKE(fc2, OUT * 128 + OUT)
-  o = par ? L.in1 : L.in0;
-  if (zs > 0) {  // Z is an input: one copy per parity, the next graph's DMA'd under this graph's tail
-    TAKE(z, N * c.LDW)
-  } else {
-    TAKE(x, N * c.XS)
-    TAKE(rp, N + 1)
-    TAKE(col, (E + 1) / 2)
-  }
-  TAKE(cl0, N)
-  TAKE(p1rp, K0 + 1)
-  TAKE(p1c, P1)
-  if (alias) {
-    c.p1trp = c.p1rp;
-    c.p1tc = c.p1c;
-  } else {
-    TAKE(p1trp, K0 + 1)
-    TAKE(p1tc, P1)
-  }
-  TAKE(m1p, K1 + 1)
-  TAKE(m1i, K0)
-  o = L.scr;
-  if (zs <= 0) TAKE(z, N * c.LDW)
-  TAKE(key, 2 * K0 * 32)
-  TAKE(p1, K0 * 32)
-  TAKE(a1, K0 * 32)
-  TAKE(dp1, K0 * 32)
-  TAKE(y2, K0 * 64)
-  TAKE(h2, K0 * 64)
-  TAKE(p2, K1 * 64)
-  TAKE(nt, K1 * 64)
-  TAKE(cl1, K0)
-  TAKE(head, HEADW)
-  TAKE(dgp, NW * 64)
-  TAKE(keep, 32)
-#undef TAKE
-  c.total = o;
+  carve_strides(c, F, zs);
+  LdsWalk w;
+  acc_take_weights(c, w, F, OUT);
+  w.o = par ? L.in1 : L.in0;
+  acc_take_inputs(c, w, N, E, K0, P1, K1, alias, zs);
+  w.o = L.scr;
+  acc_take_scratch(c, w, N, K0, K1, zs);
+  c.total = w.o;
   return c;
 }
 
-// the layout for the batch maxima (every graph's carve_acc fits inside it)
-__host__ __device__ inline AccLayout acc_layout(int Nm, int Em, int F, int K0m, int P1m, int K1m, int alias, int OUT,
+// the layout for the batch maxima: the segments' starts and the total
+__host__ __device__ __forceinline__ AccLayout acc_layout(int Nm, int Em, int F, int K0m, int P1m, int K1m, int alias, int OUT,
                                                 int zs = 0) {
   AccLayout L;
-  L.in0 = r4(32 * F) + 1024 + r4(OUT * 128 + OUT);
-  const int XS = r4(F), LDW = zs > 0 ? zs : (F <= 32 ? 32 : 64) + 2;
-  const int in = (zs > 0 ? r4(Nm * LDW) : r4(Nm * XS) + r4(Nm + 1) + r4((Em + 1) / 2)) + r4(Nm) + r4(K0m + 1) + r4(P1m) +
-                 (alias ? 0 : r4(K0m + 1) + r4(P1m)) + r4(K1m + 1) + r4(K0m);
-  L.in1 = L.in0 + in;
-  L.scr = L.in1 + in;
-  L.total = L.scr + (zs > 0 ? 0 : r4(Nm * LDW)) + r4(2 * K0m * 32) + 3 * r4(K0m * 32) + 2 * r4(K0m * 64) + 2 * r4(K1m * 64) + r4(K0m) +
-            r4(HEADW) + r4(NW * 64) + r4(32);
+  Carve c;
+  carve_strides(c, F, zs);
+  LdsWalk w;
+  acc_take_weights(c, w, F, OUT);
+  L.in0 = w.o;
+  acc_take_inputs(c, w, Nm, Em, K0m, P1m, K1m, alias, zs);
+  L.in1 = w.o;
+  L.scr = L.in1 + (L.in1 - L.in0);
+  w.o = L.scr;
+  acc_take_scratch(c, w, Nm, K0m, K1m, zs);
+  L.total = w.o;
   return L;
 }
 
@@ -236,104 +235,6 @@ struct GinetArgs {
   int32_t z_stride = 0;
   const float* z = nullptr;
 };
-
-// torch relu keeps NaN (clamp_min propagates it); its backward masks where
-// the output is <= 0 (threshold_backward), so a NaN output passes the grad.
-__device__ __forceinline__ float relu_keepnan(float v) { return (v <= 0.f) ? 0.f : v; }
-__device__ __forceinline__ float relu_bwd(float out, float g) { return (out <= 0.f) ? 0.f : g; }
-
-
-#define AS1(p) ((const __attribute__((address_space(1))) void*)(p))
-#define AS3(p) ((__attribute__((address_space(3))) void*)(p))
-
-// Asynchronous global->LDS copy of n 4-byte words (global_load_lds_dword: one
-// wave instruction moves 256 contiguous bytes, no VGPR round trip).  The LDS
-// base handed to the instruction (M0) is wave-uniform; lane l lands at base+4l.
-// w0: the wave that takes the first 64 lanes (the copies of a staging
-// sequence start on different waves, so the short ones do not all queue on
-// wave 0: an LDS DMA instruction holds its wave ~a few hundred cycles at issue)
-__device__ __forceinline__ void dma_words(void* lds_dst, const void* gsrc, int n, int tid = threadIdx.x, int w0 = 0) {
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(((tid >> 6) - w0) & (NW - 1));
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(gsrc);
-  uint32_t* dst = reinterpret_cast<uint32_t*>(lds_dst);
-  for (int base = wave * 64; base < n; base += NT)
-    if (base + lane < n) __builtin_amdgcn_global_load_lds(AS1(src + base + lane), AS3(dst + base), 4, 0, 0);
-}
-
-// Same with 16-byte lanes (global_load_lds_dwordx4, 1 KiB per wave
-// instruction).  Source and destination 16-byte aligned; n4 = 16-byte units.
-__device__ __forceinline__ void dma_x4(void* lds_dst, const void* gsrc, int n4, int tid = threadIdx.x, int w0 = 0) {
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(((tid >> 6) - w0) & (NW - 1));
-  const uint4* src = reinterpret_cast<const uint4*>(gsrc);
-  uint4* dst = reinterpret_cast<uint4*>(lds_dst);
-  for (int base = wave * 64; base < n4; base += NT)
-    if (base + lane < n4) __builtin_amdgcn_global_load_lds(AS1(src + base + lane), AS3(dst + base), 16, 0, 0);
-}
-
-// One LDS-DMA instruction from inline asm (M0 = the wave's LDS destination,
-// saved and restored around it: M0 is a reserved register the compiler may be
-// using)
-__device__ __forceinline__ void lds_dma_dword(uint32_t m0, const void* src) {
-  uint32_t saved;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(saved)
-               : "s"(m0), "v"(src));
-}
-__device__ __forceinline__ void lds_dma_x4(uint32_t m0, const void* src) {
-  uint32_t saved;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(saved)
-               : "s"(m0), "v"(src));
-}
-
-// The same copies issued from inline asm: the compiler does not know they
-// write LDS, so it inserts no wait for them before later LDS reads (with the
-// builtin it waits for the DMA before the next LDS access), and (no memory
-// clobber) reloads nothing around them.  For copies into
-// LDS no one reads until an explicit s_waitcnt vmcnt(0) + barrier: the
-// accumulating pass's prefetch of the next graph's inputs under this graph's
-// tail.
-__device__ __forceinline__ void dma_words_async(void* lds_dst, const void* gsrc, int n, int tid, int w0 = 0) {
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(((tid >> 6) - w0) & (NW - 1));
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(gsrc);
-  const uint32_t dst = (uint32_t)(size_t)AS3(lds_dst);
-  for (int base = wave * 64; base < n; base += NT)
-    if (base + lane < n)
-      lds_dma_dword(__builtin_amdgcn_readfirstlane(dst + 4 * base), src + base + lane);
-}
-
-// the same over waves [wf, wf + nw) only (the others skip)
-__device__ __forceinline__ void dma_words_async_sub(void* lds_dst, const void* gsrc, int n, int tid, int wf, int nw) {
-  const int lane = tid & 63, rw = __builtin_amdgcn_readfirstlane((tid >> 6) - wf);
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(gsrc);
-  const uint32_t dst = (uint32_t)(size_t)AS3(lds_dst);
-  if (rw < 0) return;
-  for (int base = rw * 64; base < n; base += nw * 64)
-    if (base + lane < n)
-      lds_dma_dword(__builtin_amdgcn_readfirstlane(dst + 4 * base), src + base + lane);
-}
-__device__ __forceinline__ void dma_x4_async_sub(void* lds_dst, const void* gsrc, int n4, int tid, int wf, int nw) {
-  const int lane = tid & 63, rw = __builtin_amdgcn_readfirstlane((tid >> 6) - wf);
-  const uint4* src = reinterpret_cast<const uint4*>(gsrc);
-  const uint32_t dst = (uint32_t)(size_t)AS3(lds_dst);
-  if (rw < 0) return;
-  for (int base = rw * 64; base < n4; base += nw * 64)
-    if (base + lane < n4)
-      lds_dma_x4(__builtin_amdgcn_readfirstlane(dst + 16 * base), src + base + lane);
-}
-
-__device__ __forceinline__ void dma_x4_async(void* lds_dst, const void* gsrc, int n4, int tid, int w0 = 0) {
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(((tid >> 6) - w0) & (NW - 1));
-  const uint4* src = reinterpret_cast<const uint4*>(gsrc);
-  const uint32_t dst = (uint32_t)(size_t)AS3(lds_dst);
-  for (int base = wave * 64; base < n4; base += NT)
-    if (base + lane < n4)
-      lds_dma_x4(__builtin_amdgcn_readfirstlane(dst + 16 * base), src + base + lane);
-}
-
-__device__ __forceinline__ float4 f4add(float4 a, float4 v) {
-  return make_float4(a.x + v.x, a.y + v.y, a.z + v.z, a.w + v.w);
-}
 
 // ---- the head's fc1.weight [128, 64] in the two register layouts ginet_head reads ----
 //   row layout:    thread t holds W[t >> 3][8 * (t & 7) .. + 7]   (wave w: rows 8w .. 8w + 7, whole)
@@ -382,11 +283,11 @@ __device__ __forceinline__ void w1_stage(float* sW1, float* img, const dr_ginet_
     const int base = __builtin_amdgcn_readfirstlane(tid & ~63);
     if (src >= 0) {
       const float* g = tid < 512 ? w.w1 + src : w.w1e + (src - 16 * F);  // (planes 0, 1: W1; 2, 3: W1e)
-      __builtin_amdgcn_global_load_lds(AS1(g), AS3(img + base), 4, 0, 0);
+      __builtin_amdgcn_global_load_lds(DRK_AS1(g), DRK_AS3(img + base), 4, 0, 0);
     }
   } else {
-    dma_words(sW1, w.w1, 16 * F, tid, DR_DMA_ROT * 5);  // [W1; W1e] rows of F, packed
-    dma_words(sW1 + 16 * F, w.w1e, 16 * F, tid, DR_DMA_ROT * 14);
+    dma_copy<NT, 4>(sW1, w.w1, 16 * F, tid);  // [W1; W1e] rows of F, packed
+    dma_copy<NT, 4>(sW1 + 16 * F, w.w1e, 16 * F, tid);
   }
 }
 // the image's zero words (k >= F), by plain stores beside the DMA
@@ -415,44 +316,6 @@ __device__ __forceinline__ void w1_operands(const float* sW1, const float* img, 
       const int kk = 16 * (j >> 2) + 4 * (j & 3) + kq;
       wa[j] = kk < F ? sW1[li * F + kk] : 0.f;
       wb[j] = kk < F ? sW1[(16 + li) * F + kk] : 0.f;
-    }
-  }
-}
-
-// Z[i, :XS] = sum over CSR row i of X[col[e], :XS] (edges in CSR order, i.e.
-// the order torch_scatter's CPU scatter_add_ visits them).  8 lanes per row,
-// one float4 chunk each (a 16-lane ds_read_b128 group then touches 2 rows, not
-// 4); edges unrolled by 4 so 4 index reads and then their row reads are in
-// flight together.  Z rows have the stride ldz of the MFMA operand layout.
-__device__ __forceinline__ void gather_rows(const int* rp, const uint16_t* col, const float* X, int XS, float* Z,
-                                            int ldz, int n, int tid = threadIdx.x) {
-  const int nch = XS >> 2;
-  const int sub = tid & 7;
-  for (int i = tid >> 3; i < n; i += NT / 8) {
-    const int eb = rp[i], ee = rp[i + 1];
-    for (int ch = sub; ch < nch; ch += 8) {
-      const int c4 = ch * 4;
-      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      int e = eb;
-      for (; e + 4 <= ee; e += 4) {
-        // Keep four separate 16-bit reads: hipcc would otherwise merge them
-        // into one ds_read_b64 that is misaligned for 3 of 4 row starts (LDS
-        // replays those at ~64 cycles).  The empty asm hides the contiguity.
-        int e1 = e + 1, e2 = e + 2, e3 = e + 3;
-        asm volatile("" : "+v"(e1), "+v"(e2), "+v"(e3));
-        const int j0 = col[e], j1 = col[e1], j2 = col[e2], j3 = col[e3];
-        const float4 v0 = *reinterpret_cast<const float4*>(&X[__umul24(j0, XS) + c4]);
-        const float4 v1 = *reinterpret_cast<const float4*>(&X[__umul24(j1, XS) + c4]);
-        const float4 v2 = *reinterpret_cast<const float4*>(&X[__umul24(j2, XS) + c4]);
-        const float4 v3 = *reinterpret_cast<const float4*>(&X[__umul24(j3, XS) + c4]);
-        acc = f4add(f4add(f4add(f4add(acc, v0), v1), v2), v3);
-      }
-      for (; e < ee; ++e) acc = f4add(acc, *reinterpret_cast<const float4*>(&X[__umul24((int)col[e], XS) + c4]));
-      float* zr = Z + i * ldz + c4;
-      zr[0] = acc.x;
-      zr[1] = acc.y;
-      zr[2] = acc.z;
-      zr[3] = acc.w;
     }
   }
 }
@@ -517,9 +380,6 @@ struct TailLds {
   // [dW1cat 32F | dW2cat 1024 | the head's, GinetHeadLds::acc], or null
   float* acc = nullptr;
   float* accf = nullptr;  // GinetHeadLds::accf
-  // or null: the depth-0 pooling keys, P1 not yet decoded (conv2 decodes the
-  // rows it reads; the decode runs beside it in the same step)
-  const unsigned long long* key = nullptr;
   // p2's first row zeroed by the caller before its last barrier: with one
   // depth-1 cluster (K1 = 1, K0 < 16) conv2 folds the depth-1 max into it by
   // LDS atomic max, and the pooling and mean steps go
@@ -556,7 +416,7 @@ __device__ __forceinline__ TailLds tail_lds(const C& c, float* lds) {
   return t;
 }
 
-template <class ZAt, bool WT = false, bool ACC = false>
+template <class ZAt, bool ACC = false>
 __device__ __forceinline__ void ginet_tail(const GinetArgs& a, const TailLds& t, const float (&fc1_row)[8],
                                            const float (&fc1_col)[8], float fc1_bias, int b, int N, int K0, int K1,
                                            int F, int OUT, float y_g, uint64_t drop_offset, ZAt zat, int pb) {
@@ -586,26 +446,14 @@ __device__ __forceinline__ void ginet_tail(const GinetArgs& a, const TailLds& t,
     float acc = 0.f;
     for (int e = t.p1rp[k]; e < t.p1rp[k + 1]; ++e) {
       float y = 0.f;
-      if (t.key) {  // P1 = the key's value half, 0 for an empty (cluster, channel)
-        const unsigned long long* kr = t.key + t.p1c[e] * 32 + br * 16;
+      const float* pr = t.p1 + t.p1c[e] * 32 + br * 16;
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const ulonglong2 kv = *reinterpret_cast<const ulonglong2*>(kr + 2 * q);
-          const float v0 = kv.x ? __uint_as_float((uint32_t)(kv.x >> 32)) : 0.f;
-          const float v1 = kv.y ? __uint_as_float((uint32_t)(kv.y >> 32)) : 0.f;
-          y = fmaf(v0, wr[2 * q], y);
-          y = fmaf(v1, wr[2 * q + 1], y);
-        }
-      } else {
-        const float* pr = t.p1 + t.p1c[e] * 32 + br * 16;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 v = *reinterpret_cast<const float4*>(pr + 4 * q);
-          y = fmaf(v.x, wr[4 * q], y);
-          y = fmaf(v.y, wr[4 * q + 1], y);
-          y = fmaf(v.z, wr[4 * q + 2], y);
-          y = fmaf(v.w, wr[4 * q + 3], y);
-        }
+      for (int q = 0; q < 4; ++q) {
+        const float4 v = *reinterpret_cast<const float4*>(pr + 4 * q);
+        y = fmaf(v.x, wr[4 * q], y);
+        y = fmaf(v.y, wr[4 * q + 1], y);
+        y = fmaf(v.z, wr[4 * q + 2], y);
+        y = fmaf(v.w, wr[4 * q + 3], y);
       }
       acc += y;
     }
@@ -731,7 +579,7 @@ __device__ __forceinline__ void ginet_tail(const GinetArgs& a, const TailLds& t,
     hl.acc = ACC ? t.acc + 32 * F + 1024 : nullptr;
     hl.accf = ACC ? t.accf : nullptr;
     hl.dg_deferred = true;  // summed from dgp by the pooling backward below
-    if (!drk::ginet_head<NT, WT, ACC>(a.p, hl, fc1_row, fc1_col, fc1_bias, b, OUT, y_g, drop_offset, 8, pb)) return;
+    if (!drk::ginet_head<NT, ACC>(a.p, hl, fc1_row, fc1_col, fc1_bias, b, OUT, y_g, drop_offset, 8, pb)) return;
   }  // stamps 8 (forward head done) and 9 (loss gradient done) are taken inside
 
   STAMP(10);
@@ -790,7 +638,7 @@ __device__ __forceinline__ void ginet_tail(const GinetArgs& a, const TailLds& t,
       }
       for (; k < K0; ++k) acc = fmaf(t.y2[k * 64 + o], t.p1[k * 32 + br * 16 + j], acc);
       if (ACC) t.acc[32 * F + p] += acc;
-      else drk::st_part<WT>(slab + p, acc);
+      else drk::st_part(slab + p, acc);
     }
     for (int p = tid; p < K0 * 32; p += NT) {
       const int k = p >> 5, ch = p & 31, br = ch >> 4, j = ch & 15;
@@ -824,7 +672,7 @@ __device__ __forceinline__ void ginet_tail(const GinetArgs& a, const TailLds& t,
           for (int r = 0; r < 4; ++r) t.acc[32 * F + br * 512 + (ot * 16 + kq * 4 + r) * 16 + li] = o[r] + acc[r];
         } else {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) drk::st_part<WT>(slab + br * 512 + (ot * 16 + kq * 4 + r) * 16 + li, acc[r]);
+          for (int r = 0; r < 4; ++r) drk::st_part(slab + br * 512 + (ot * 16 + kq * 4 + r) * 16 + li, acc[r]);
         }
       } else {
         const int q = job - 4, br = q & 1, r0 = (q >> 1) * 16;
@@ -881,7 +729,7 @@ __device__ __forceinline__ void ginet_tail(const GinetArgs& a, const TailLds& t,
             if (ok[u]) acc = fmaf(dv[u], zv[u], acc);
         }
         if (ACC) t.acc[p] += acc;
-        else drk::st_part<WT>(slab + p, acc);
+        else drk::st_part(slab + p, acc);
       }
     };
     if (K0 > 8) dw1(std::integral_constant<int, 16>());  // (all of K0 <= 32 in flight at once: +0.6 us atom, not kept)
@@ -1000,7 +848,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   float fc1_row[8], fc1_col[8], fc1_bias;
   // conv1's B operands as a lane-ordered image in dgp (free until the head;
   // PF stages the weights once per workgroup and reuses dgp per graph: packed rows)
-  constexpr bool IMG = DR_W1_IMAGE && KPT == 32 && !PF;
+  constexpr bool IMG = KPT == 32 && !PF;
   float* sImg = lds + c.dgp;
   float wv2, wfc[3];
   auto load_head_weights = [&]() {
@@ -1025,45 +873,48 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   uint64_t drop_offset = a.p.drop_offset;
   // the graph's inputs (PF: graph k+1's are DMA'd during graph k's tail)
   // (asm-issued: waited for by the s_waitcnt vmcnt(0) before the staging barrier)
+  // (The three stagings below stay written out: driven from one list of the
+  // inputs they cost ginet_multi_kernel 0.15 us per step,
+  // profiles/dead_variants/staging_variants.txt.)
   auto stage_inputs = [&](const dr_graph_desc& dd, const Carve& cc) {
     const int64_t dn0 = dd.node0, dk00 = dd.k0;
     const int dg = dd.gid, dN = dd.n_nodes, dK0 = dd.n_k0;
     if (ZIN) {  // the graph's Z block as it lies in HBM (16-byte lanes where the stride gives 16-byte rows)
-      if ((LDW & 3) == 0) dma_x4_async(lds + cc.z, a.z + dn0 * (int64_t)LDW, dN * LDW / 4, tid);
-      else dma_words_async(lds + cc.z, a.z + dn0 * (int64_t)LDW, dN * LDW, tid);
+      if ((LDW & 3) == 0) dma_copy<NT, 16, DMA_ASM>(lds + cc.z, a.z + dn0 * (int64_t)LDW, dN * LDW / 4, tid);
+      else dma_copy<NT, 4, DMA_ASM>(lds + cc.z, a.z + dn0 * (int64_t)LDW, dN * LDW, tid);
     } else {
-      dma_x4_async(lds + cc.x, s.x + dn0 * (int64_t)XS, dN * XS / 4, tid);
-      dma_x4_async(lds + cc.col, s.col + dd.col0, (dd.n_edges + 7) / 8, tid, 7);
-      dma_words_async(lds + cc.rp, s.rowptr + dn0 + dg, dN + 1, tid, 13);
+      dma_copy<NT, 16, DMA_ASM>(lds + cc.x, s.x + dn0 * (int64_t)XS, dN * XS / 4, tid);
+      dma_copy<NT, 16, DMA_ASM>(lds + cc.col, s.col + dd.col0, (dd.n_edges + 7) / 8, tid, 7);
+      dma_copy<NT, 4, DMA_ASM>(lds + cc.rp, s.rowptr + dn0 + dg, dN + 1, tid, 13);
     }
-    dma_words_async(lds + cc.cl0, s.cl0 + dn0, dN, tid, 3);
-    dma_words_async(lds + cc.p1rp, s.p1_rowptr + dk00 + dg, dK0 + 1, tid, 10);
-    dma_words_async(lds + cc.p1c, s.p1_col + dd.p1, dd.n_p1, tid, 11);
+    dma_copy<NT, 4, DMA_ASM>(lds + cc.cl0, s.cl0 + dn0, dN, tid, 3);
+    dma_copy<NT, 4, DMA_ASM>(lds + cc.p1rp, s.p1_rowptr + dk00 + dg, dK0 + 1, tid, 10);
+    dma_copy<NT, 4, DMA_ASM>(lds + cc.p1c, s.p1_col + dd.p1, dd.n_p1, tid, 11);
     if (!alias) {
-      dma_words_async(lds + cc.p1trp, s.p1t_rowptr + dk00 + dg, dK0 + 1, tid, 12);
-      dma_words_async(lds + cc.p1tc, s.p1t_col + dd.p1, dd.n_p1, tid, 9);
+      dma_copy<NT, 4, DMA_ASM>(lds + cc.p1trp, s.p1t_rowptr + dk00 + dg, dK0 + 1, tid, 12);
+      dma_copy<NT, 4, DMA_ASM>(lds + cc.p1tc, s.p1t_col + dd.p1, dd.n_p1, tid, 9);
     }
-    dma_words_async(lds + cc.m1p, s.m1_ptr + dd.k1 + dg, dd.n_k1 + 1, tid, 8);
-    dma_words_async(lds + cc.m1i, s.m1_idx + dk00, dK0, tid, 1);
+    dma_copy<NT, 4, DMA_ASM>(lds + cc.m1p, s.m1_ptr + dd.k1 + dg, dd.n_k1 + 1, tid, 8);
+    dma_copy<NT, 4, DMA_ASM>(lds + cc.m1i, s.m1_idx + dk00, dK0, tid, 1);
   };
-  if (!PF) {  // (DR_DMA_ROT = 1: starting waves spread over the copies; measured slower)
+  if (!PF) {  // (every copy from wave 0: starting waves spread over the copies measured slower)
     if (ZIN) {
-      if ((LDW & 3) == 0) dma_x4(sZ, a.z + n0 * (int64_t)LDW, N * LDW / 4, tid);
-      else dma_words(sZ, a.z + n0 * (int64_t)LDW, N * LDW, tid);
+      if ((LDW & 3) == 0) dma_copy<NT, 16>(sZ, a.z + n0 * (int64_t)LDW, N * LDW / 4, tid);
+      else dma_copy<NT, 4>(sZ, a.z + n0 * (int64_t)LDW, N * LDW, tid);
     } else {
-      dma_x4(sX, s.x + n0 * (int64_t)XS, N * XS / 4, tid);
-      dma_x4(scol, s.col + ec0, (E + 7) / 8, tid, DR_DMA_ROT * 7);
-      dma_words(srp, s.rowptr + n0 + g, N + 1, tid, DR_DMA_ROT * 13);
+      dma_copy<NT, 16>(sX, s.x + n0 * (int64_t)XS, N * XS / 4, tid);
+      dma_copy<NT, 16>(scol, s.col + ec0, (E + 7) / 8, tid);
+      dma_copy<NT, 4>(srp, s.rowptr + n0 + g, N + 1, tid);
     }
-    dma_words(scl0, s.cl0 + n0, N, tid, DR_DMA_ROT * 3);
-    dma_words(sp1rp, s.p1_rowptr + k00 + g, K0 + 1, tid, DR_DMA_ROT * 10);
-    dma_words(sp1c, s.p1_col + q0, P1, tid, DR_DMA_ROT * 11);
+    dma_copy<NT, 4>(scl0, s.cl0 + n0, N, tid);
+    dma_copy<NT, 4>(sp1rp, s.p1_rowptr + k00 + g, K0 + 1, tid);
+    dma_copy<NT, 4>(sp1c, s.p1_col + q0, P1, tid);
     if (!alias) {
-      dma_words(sp1trp, s.p1t_rowptr + k00 + g, K0 + 1, tid, DR_DMA_ROT * 12);
-      dma_words(sp1tc, s.p1t_col + q0, P1, tid, DR_DMA_ROT * 9);
+      dma_copy<NT, 4>(sp1trp, s.p1t_rowptr + k00 + g, K0 + 1, tid);
+      dma_copy<NT, 4>(sp1tc, s.p1t_col + q0, P1, tid);
     }
-    dma_words(sm1p, s.m1_ptr + k10 + g, K1 + 1, tid, DR_DMA_ROT * 8);
-    dma_words(sm1i, s.m1_idx + k00, K0, tid, DR_DMA_ROT * 1);
+    dma_copy<NT, 4>(sm1p, s.m1_ptr + k10 + g, K1 + 1, tid);
+    dma_copy<NT, 4>(sm1i, s.m1_idx + k00, K0, tid);
   } else if (ac.first || *ac.staged == 0u) {
     stage_inputs(d, c);
   }
@@ -1073,7 +924,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   // here, beside the staging DMA, and arrive with it: 10.50 -> 10.25 us per
   // pass.  (Only W2 / fc2 here and fc1's 64 KB of registers after the barrier:
   // 10.6 us, profiles/r07.)
-  if (ZIN && DR_ZIN_EARLY_W) load_head_weights();
+  if (ZIN) load_head_weights();
   {  // zero Z's K padding (cols XS..KPT; X's own pad is zero) and the pooling keys
     const int padz = KPT - XS;  // (rows are KP = KPT wide, carve; ZIN: the array's rows arrive whole)
     if (!ZIN)
@@ -1098,7 +949,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   // VGPRs now and store them to LDS after the front half, so their latency
   // overlaps it.  (An LDS DMA here would make hipcc wait for it before every
   // LDS read.)
-  if (!(ZIN && DR_ZIN_EARLY_W)) load_head_weights();
+  if (!ZIN) load_head_weights();
   // ---------------- conv1 + depth-0 pooling, one 16-row tile per wave -------
   // Each wave runs its rows through the whole front half with no workgroup
   // barrier in between:
@@ -1137,35 +988,30 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
         const int nw = NW - busy;
         const int64_t dn0 = dn.node0, dk00 = dn.k0;
         const int dg = dn.gid, dN = dn.n_nodes, dK0 = dn.n_k0;
-        dma_x4_async_sub(lds + cn.x, s.x + dn0 * (int64_t)XS, dN * XS / 4, tid, busy, nw);
-        dma_x4_async_sub(lds + cn.col, s.col + dn.col0, (dn.n_edges + 7) / 8, tid, busy, nw);
-        dma_words_async_sub(lds + cn.rp, s.rowptr + dn0 + dg, dN + 1, tid, busy, nw);
-        dma_words_async_sub(lds + cn.cl0, s.cl0 + dn0, dN, tid, busy, nw);
-        dma_words_async_sub(lds + cn.p1rp, s.p1_rowptr + dk00 + dg, dK0 + 1, tid, busy, nw);
-        dma_words_async_sub(lds + cn.p1c, s.p1_col + dn.p1, dn.n_p1, tid, busy, nw);
+        dma_copy<NT, 16, DMA_ASM>(lds + cn.x, s.x + dn0 * (int64_t)XS, dN * XS / 4, tid, busy, nw);
+        dma_copy<NT, 16, DMA_ASM>(lds + cn.col, s.col + dn.col0, (dn.n_edges + 7) / 8, tid, busy, nw);
+        dma_copy<NT, 4, DMA_ASM>(lds + cn.rp, s.rowptr + dn0 + dg, dN + 1, tid, busy, nw);
+        dma_copy<NT, 4, DMA_ASM>(lds + cn.cl0, s.cl0 + dn0, dN, tid, busy, nw);
+        dma_copy<NT, 4, DMA_ASM>(lds + cn.p1rp, s.p1_rowptr + dk00 + dg, dK0 + 1, tid, busy, nw);
+        dma_copy<NT, 4, DMA_ASM>(lds + cn.p1c, s.p1_col + dn.p1, dn.n_p1, tid, busy, nw);
         if (!alias) {
-          dma_words_async_sub(lds + cn.p1trp, s.p1t_rowptr + dk00 + dg, dK0 + 1, tid, busy, nw);
-          dma_words_async_sub(lds + cn.p1tc, s.p1t_col + dn.p1, dn.n_p1, tid, busy, nw);
+          dma_copy<NT, 4, DMA_ASM>(lds + cn.p1trp, s.p1t_rowptr + dk00 + dg, dK0 + 1, tid, busy, nw);
+          dma_copy<NT, 4, DMA_ASM>(lds + cn.p1tc, s.p1t_col + dn.p1, dn.n_p1, tid, busy, nw);
         }
-        dma_words_async_sub(lds + cn.m1p, s.m1_ptr + dn.k1 + dg, dn.n_k1 + 1, tid, busy, nw);
-        dma_words_async_sub(lds + cn.m1i, s.m1_idx + dk00, dK0, tid, busy, nw);
+        dma_copy<NT, 4, DMA_ASM>(lds + cn.m1p, s.m1_ptr + dn.k1 + dg, dn.n_k1 + 1, tid, busy, nw);
+        dma_copy<NT, 4, DMA_ASM>(lds + cn.m1i, s.m1_idx + dk00, dK0, tid, busy, nw);
       }
       if (tid == 0) *ac.staged = (ac.next >= 0 && busy < NW) ? 1u : 0u;
     }
     for (int tt = wave; tt * 16 < N; tt += NW) {
       const int r0 = tt * 16;
       if (!ZIN) {
-#if DR_GATHER_ROW2
       if (nch <= 8) {  // one row per lane (r0 + lane/4), chunks q and q ^ 4 (q = lane%4, or +4 on odd rows)
         const int i = r0 + (lane >> 2);
         const int ca = (lane & 3) | ((lane & 4)), cb = ca ^ 4;
         const int eb = i < N ? srp[i] : 0, ee = i < N ? srp[i + 1] : 0;
         float4 za, zb;
-#if DR_GATHER_IMM
         drk::gather_row_two_chunks_imm(scol, eb, ee, reinterpret_cast<const char*>(sX + ca * 4), (cb - ca) * 16, XS * 4, za, zb);
-#else
-        drk::gather_row_two_chunks(scol, eb, ee, sX, XS, ca * 4, cb * 4, za, zb);
-#endif
         if (i < N) {
           // (rows LDW = KP + 2 words apart: 8-byte aligned, two 64-bit stores per chunk)
           if (ca < nch) {
@@ -1179,9 +1025,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
             zr[1] = make_float2(zb.z, zb.w);
           }
         }
-      } else
-#endif
-      {  // rows r0+slot and r0+8+slot together: two independent edge chains per lane
+      } else {  // rows r0+slot and r0+8+slot together: two independent edge chains per lane
         const int i0 = r0 + slot, i1 = r0 + 8 + slot;
         const int eb0 = i0 < N ? srp[i0] : 0, ee0 = i0 < N ? srp[i0 + 1] : 0;
         const int eb1 = i1 < N ? srp[i1] : 0, ee1 = i1 < N ? srp[i1 + 1] : 0;
@@ -1274,17 +1118,14 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   STAMP(2);
   __syncthreads();
   STAMP(3);
-  // (no barrier after the decode: conv2, the tail's first step, reads the
-  // pooled rows from the keys themselves — TailLds::key)
   for (int p = tid; p < K0 * 32; p += NT) {
     const unsigned long long key = skey[p];
     sP1[p] = key ? __uint_as_float((uint32_t)(key >> 32)) : 0.f;
     sA1[p] = key ? (int)(0xffffffffu - (uint32_t)key) : N;
   }
-  if (!DR_CONV2_KEYS) __syncthreads();
+  __syncthreads();  // (conv2 reading the pooled rows from the keys, with no barrier here, measured 0.1 us slower)
 
   TailLds t = tail_lds(c, lds);
-  t.key = !DR_CONV2_KEYS ? nullptr : skey;
   t.p2_zeroed = true;
   t.keep = skeep;
   t.acc = ACC ? ac.acc : nullptr;
@@ -1292,7 +1133,7 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   auto zat = [&](int i, int kk) { return sZ[i * LDW + kk]; };
   // (dr_pass.slot: the graph's rows of the batch when it is split over launches)
   const int orow = a.p.slot ? a.p.slot[b] : b;
-  ginet_tail<decltype(zat), false, ACC>(a, t, fc1_row, fc1_col, fc1_bias, orow, N, K0, K1, F, OUT, y_g, drop_offset, zat, orow);
+  ginet_tail<decltype(zat), ACC>(a, t, fc1_row, fc1_col, fc1_bias, orow, N, K0, K1, F, OUT, y_g, drop_offset, zat, orow);
   return drop_offset;
 }
 
@@ -1359,8 +1200,8 @@ __global__ void __launch_bounds__(NT) ginet_input_grad_kernel(GinetArgs a, dr_in
   const float* dp1 = lds + c.dp1;
   const int* a1 = reinterpret_cast<const int*>(lds + c.a1);
   for (int p = tid; p < N * c.LDW; p += NT) dZ[p] = 0.f;
-  dma_words(trp, a.s.t_rowptr + d.node0 + d.gid, N + 1, tid);
-  dma_x4(tcol, a.s.t_col + d.col0, (E + 7) / 8, tid, 7);
+  dma_copy<NT, 4>(trp, a.s.t_rowptr + d.node0 + d.gid, N + 1, tid);
+  dma_copy<NT, 16>(tcol, a.s.t_col + d.col0, (E + 7) / 8, tid, 7);
   const int64_t row0 = ig.row_off[b];
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -1590,48 +1431,22 @@ __device__ __forceinline__ int lower_bound_lds(const int* v, int lo, int hi, int
   return lo;
 }
 
-// Global-address-space views for in-launch hand-offs (MI355X_MICROARCH.md
-// §inter-workgroup visibility): agent-scope relaxed atomics lower to sc1
-// global loads/stores, which bypass the per-CU L1 and write through the
-// per-XCD L2, so a payload stored this way, drained (s_waitcnt vmcnt(0)) and
-// signalled by an agent-scope counter add is read correctly by the workgroup
-// whose add came last with sc1 loads, wherever the two sit.
-
-template <bool INL>
-__device__ __forceinline__ void store_u64(void* p, uint64_t v) {
-  if (INL) __hip_atomic_store((gu64*)(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *reinterpret_cast<uint64_t*>(p) = v;
-}
-template <bool INL>
-__device__ __forceinline__ void store_z4(float* p, float4 v) {
-  if (INL) {
-    store_u64<true>(p, (uint64_t)__float_as_uint(v.x) | ((uint64_t)__float_as_uint(v.y) << 32));
-    store_u64<true>(p + 2, (uint64_t)__float_as_uint(v.z) | ((uint64_t)__float_as_uint(v.w) << 32));
-  } else {
-    *reinterpret_cast<float4*>(p) = v;
-  }
-}
-__device__ __forceinline__ uint32_t load_sc1_u32(const void* p) {
-  return __hip_atomic_load((const gu32*)(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // The tile's partial depth-0 max per (cluster, channel) of H (LDS, stride
 // 32, rows r0..r0+nrows-1): strict '>' in node order, first max wins, NaN never
 // enters (torch_scatter scatter_max, community_pooling.py:209).  Published by
 // 64-bit atomic max keys or per-tile partials (dr_large_plan).
-template <int NTT, bool INL>
 __device__ __forceinline__ void tile_partial_max(const dr_large_plan& pl, const float* sH, const int* sm0i,
                                                  const int* sm0p, int* srng, bool compact, int tile, int b, int K0,
-                                                 int N, int r0, int nrows, int* sflag = nullptr) {
+                                                 int N, int r0, int nrows, int* sflag) {
   const int tid = threadIdx.x;
   // each cluster's members inside this tile: a sub-run of its ascending list
-  for (int k = tid; k < K0; k += NTT) {
+  for (int k = tid; k < K0; k += NTA) {
     const int mb = sm0p[k], me = sm0p[k + 1];
     srng[2 * k] = compact ? mb : lower_bound_lds(sm0i, mb, me, r0);
     srng[2 * k + 1] = compact ? me : lower_bound_lds(sm0i, mb, me, r0 + nrows);
   }
   __syncthreads();
-  for (int p = tid; p < K0 * 32; p += NTT) {
+  for (int p = tid; p < K0 * 32; p += NTA) {
     const int k = p >> 5, ch = p & 31;
     float best = LOWEST;
     int arg = N;
@@ -1643,7 +1458,7 @@ __device__ __forceinline__ void tile_partial_max(const dr_large_plan& pl, const 
         arg = i;
       }
     }
-    if (sflag && arg < N) sflag[arg - r0] = 1;  // (benign race: every writer stores 1)
+    if (arg < N) sflag[arg - r0] = 1;  // (benign race: every writer stores 1)
     if (pl.part_key) {  // order-free combine over the graph's tiles (see dr_large_plan.part_key)
       if (best > LOWEST)
         __hip_atomic_fetch_max((gu64*)(pl.part_key) + ((int64_t)b * pl.k0_max + k) * 32 + ch,
@@ -1659,7 +1474,6 @@ __device__ __forceinline__ void tile_partial_max(const dr_large_plan& pl, const 
 
 // One tile of TR nodes: Z rows (CSR gather over HBM/L2), H = relu(Z W^T) on
 // MFMA, and the tile's partial depth-0 max per (cluster, channel).
-template <int NTT, bool INL>
 __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
   const GinetArgs& a = la.g;
   const dr_large_plan& pl = la.plan;
@@ -1685,28 +1499,26 @@ __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
 
   const bool compact = pl.tile_members != nullptr;
   if (compact) {  // this tile's members by cluster (host-built), runs from tile_mptr
-    drk::dma_words<NTT>(sm0i, pl.tile_members + (int64_t)tile * TRr, nrows);
-    drk::dma_words<NTT>(sm0p, pl.tile_mptr + (int64_t)tile * (pl.k0_max + 1), K0 + 1);
+    dma_copy<NTA, 4>(sm0i, pl.tile_members + (int64_t)tile * TRr, nrows);
+    dma_copy<NTA, 4>(sm0p, pl.tile_mptr + (int64_t)tile * (pl.k0_max + 1), K0 + 1);
   } else {
-    drk::dma_words<NTT>(sm0i, s.m0_idx + n0, N);
-    drk::dma_words<NTT>(sm0p, s.m0_ptr + k00 + g, K0 + 1);
+    dma_copy<NTA, 4>(sm0i, s.m0_idx + n0, N);
+    dma_copy<NTA, 4>(sm0p, s.m0_ptr + k00 + g, K0 + 1);
   }
-  for (int p = tid; p < 32 * KP; p += NTT) {  // [W1; W1e] zero-padded to KP
+  for (int p = tid; p < 32 * KP; p += NTA) {  // [W1; W1e] zero-padded to KP
     const int r = p / KP, k = p - r * KP;
     float v = 0.f;
     if (k < F) v = (r < 16) ? a.w.w1[r * F + k] : a.w.w1e[(r - 16) * F + k];
     sW1[r * LDW + k] = v;
   }
-  for (int p = tid; p < TRr * (KP - XS); p += NTT) {  // Z pad columns
+  for (int p = tid; p < TRr * (KP - XS); p += NTA) {  // Z pad columns
     const int r = p / (KP - XS);
     sZ[r * LDW + XS + (p - r * (KP - XS))] = 0.f;
   }
   // Z rows go to global memory only at the tile's depth-0 pooling arg
   // candidates (the tail reads Z at the final args, which are tile args)
-  constexpr bool ZARGS = DR_Z_ARGS && !INL;
   int* sflag = reinterpret_cast<int*>(lds + c.flg);
-  if (ZARGS)
-    for (int p = tid; p < TRr; p += NTT) sflag[p] = 0;
+  for (int p = tid; p < TRr; p += NTA) sflag[p] = 0;
   if (pl.halo_ids) {
     // Halo path: stage the tile's rowptr slice, its halo ids, then the halo X
     // rows and the tile's edges (as halo indices) into LDS; gather from LDS.
@@ -1716,17 +1528,17 @@ __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
     float* sXh = lds + c.xh;
     const int h0 = pl.halo_off[tile], H = pl.halo_off[tile + 1] - h0;
     const int l0 = pl.lcol_off[tile];
-    drk::dma_words<NTT>(strp, s.rowptr + n0 + g + r0, nrows + 1);
-    drk::dma_words<NTT>(shid, pl.halo_ids + h0, H);
+    dma_copy<NTA, 4>(strp, s.rowptr + n0 + g + r0, nrows + 1);
+    dma_copy<NTA, 4>(shid, pl.halo_ids + h0, H);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     const int ebase = strp[0];
-    drk::dma_x4<NTT>(slcol, pl.lcol + l0, (strp[nrows] - ebase + 7) / 8);
+    dma_copy<NTA, 16>(slcol, pl.lcol + l0, (strp[nrows] - ebase + 7) / 8);
     {
       const float* X = s.x + n0 * (int64_t)XS;
       const int nch = XS >> 2, tot = H * nch;
       const int wv = __builtin_amdgcn_readfirstlane(wave);
-      for (int base = wv * 64; base < tot; base += NTT)
+      for (int base = wv * 64; base < tot; base += NTA)
         if (base + lane < tot) {
           const int hr = (base + lane) / nch, ch = base + lane - hr * nch;
           __builtin_amdgcn_global_load_lds(DRK_AS1(X + (int64_t)shid[hr] * XS + ch * 4), DRK_AS3(sXh + base * 4), 16, 0, 0);
@@ -1734,9 +1546,8 @@ __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    float* zg = pl.z + (int64_t)pl.z_row0[b] * XS;
     const int nch = XS >> 2, sub = tid & 7;
-    for (int r = tid >> 3; r < nrows; r += NTT / 8) {
+    for (int r = tid >> 3; r < nrows; r += NTA / 8) {
       const int eb = strp[r] - ebase, ee = strp[r + 1] - ebase;
       for (int ch = sub; ch < nch; ch += 8) {
         const int c4 = ch * 4;
@@ -1746,7 +1557,6 @@ __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
         zr[1] = acc.y;
         zr[2] = acc.z;
         zr[3] = acc.w;
-        if (!ZARGS) store_z4<INL>(zg + (int64_t)(r0 + r) * XS + c4, acc);
       }
     }
   } else {
@@ -1755,9 +1565,8 @@ __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
     const int* rp = s.rowptr + n0 + g;
     const uint16_t* col = s.col + ec0;
     const float* X = s.x + n0 * (int64_t)XS;
-    float* zg = pl.z + (int64_t)pl.z_row0[b] * XS;
     const int nch = XS >> 2, sub = tid & 7;
-    for (int r = tid >> 3; r < nrows; r += NTT / 8) {
+    for (int r = tid >> 3; r < nrows; r += NTA / 8) {
       const int i = r0 + r;
       const int eb = rp[i], ee = rp[i + 1];
       for (int ch = sub; ch < nch; ch += 8) {
@@ -1778,20 +1587,15 @@ __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
         zr[1] = acc.y;
         zr[2] = acc.z;
         zr[3] = acc.w;
-        if (!ZARGS) store_z4<INL>(zg + (int64_t)i * XS + c4, acc);
       }
     }
   }
   }
-  // (no s_waitcnt vmcnt(0) here: the MFMA phase reads Z from LDS, and the Z
-  // stores to global memory need not land before it -- the tail reads them in
-  // the next launch.  DR_TILE_STORE_WAIT = 1 restores the wait, A/B)
-  if (DR_TILE_STORE_WAIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   // H = relu(Z [W1; W1e]^T), one 16-row MFMA tile per wave
   {
     const int li = lane & 15, kq = lane >> 4;
-    for (int tt = wave; tt * 16 < nrows; tt += NTT / 64) {
+    for (int tt = wave; tt * 16 < nrows; tt += NTA / 64) {
       const int q0 = tt * 16;
       const int ar = min(q0 + li, nrows - 1);
       floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -1820,25 +1624,23 @@ __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
       }
     }
   }
-  tile_partial_max<NTT, INL>(pl, sH, sm0i, sm0p, srng, compact, tile, b, K0, N, r0, nrows, ZARGS ? sflag : nullptr);
-  if (ZARGS) {
-    __syncthreads();
-    float* zg = pl.z + (int64_t)pl.z_row0[b] * XS;
-    const int nch = XS >> 2;
-    for (int p = tid; p < nrows * nch; p += NTT) {
-      const int r = p / nch, c4 = (p - r * nch) * 4;
-      if (sflag[r]) {
-        const float2* zr = reinterpret_cast<const float2*>(sZ + r * LDW + c4);  // (rows 8-byte aligned)
-        const float2 lo = zr[0], hi = zr[1];
-        *reinterpret_cast<float4*>(zg + (int64_t)(r0 + r) * XS + c4) = make_float4(lo.x, lo.y, hi.x, hi.y);
-      }
+  tile_partial_max(pl, sH, sm0i, sm0p, srng, compact, tile, b, K0, N, r0, nrows, sflag);
+  __syncthreads();
+  float* zg = pl.z + (int64_t)pl.z_row0[b] * XS;
+  const int nch = XS >> 2;
+  for (int p = tid; p < nrows * nch; p += NTA) {
+    const int r = p / nch, c4 = (p - r * nch) * 4;
+    if (sflag[r]) {
+      const float2* zr = reinterpret_cast<const float2*>(sZ + r * LDW + c4);  // (rows 8-byte aligned)
+      const float2 lo = zr[0], hi = zr[1];
+      *reinterpret_cast<float4*>(zg + (int64_t)(r0 + r) * XS + c4) = make_float4(lo.x, lo.y, hi.x, hi.y);
     }
   }
 }
 
 __global__ void __launch_bounds__(NTA) ginet_large_conv1_kernel(LargeArgs la) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  conv_tile_f32<NTA, false>(la, lds);
+  conv_tile_f32(la, lds);
 }
 
 // ---- bf16 compute (dr_pass.compute_dtype == DR_DTYPE_BF16, BASELINE configs[3]) ----
@@ -1903,7 +1705,6 @@ __host__ __device__ inline ConvCarveB conv_carve_bf16(int N, int F, int K0, int 
   return c;
 }
 
-template <int NTT, bool INL>
 __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) {
   const GinetArgs& a = la.g;
   const dr_large_plan& pl = la.plan;
@@ -1931,26 +1732,24 @@ __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) 
 
   const bool compact = pl.tile_members != nullptr;
   if (compact) {
-    drk::dma_words<NTT>(sm0i, pl.tile_members + (int64_t)tile * TRr, nrows);
-    drk::dma_words<NTT>(sm0p, pl.tile_mptr + (int64_t)tile * (pl.k0_max + 1), K0 + 1);
+    dma_copy<NTA, 4>(sm0i, pl.tile_members + (int64_t)tile * TRr, nrows);
+    dma_copy<NTA, 4>(sm0p, pl.tile_mptr + (int64_t)tile * (pl.k0_max + 1), K0 + 1);
   } else {
-    drk::dma_words<NTT>(sm0i, s.m0_idx + n0, N);
-    drk::dma_words<NTT>(sm0p, s.m0_ptr + k00 + g, K0 + 1);
+    dma_copy<NTA, 4>(sm0i, s.m0_idx + n0, N);
+    dma_copy<NTA, 4>(sm0p, s.m0_ptr + k00 + g, K0 + 1);
   }
-  for (int p = tid; p < 32 * KPB; p += NTT) {  // [W1; W1e] in bf16, K zero-padded to KPB
+  for (int p = tid; p < 32 * KPB; p += NTA) {  // [W1; W1e] in bf16, K zero-padded to KPB
     const int r = p / KPB, k = p - r * KPB;
     float v = 0.f;
     if (k < F) v = (r < 16) ? a.w.w1[r * F + k] : a.w.w1e[(r - 16) * F + k];
     sW[r * ZSB + k] = f2bf(v);
   }
-  for (int p = tid; p < TRr * (KPB - XSB); p += NTT) {  // Z pad columns (X's own pad is zero)
+  for (int p = tid; p < TRr * (KPB - XSB); p += NTA) {  // Z pad columns (X's own pad is zero)
     const int r = p / (KPB - XSB);
     sZ[r * ZSB + XSB + (p - r * (KPB - XSB))] = 0;
   }
-  constexpr bool ZARGS = DR_Z_ARGS && !INL;  // (as conv_tile_f32)
-  int* sflag = reinterpret_cast<int*>(lds + c.flg);
-  if (ZARGS)
-    for (int p = tid; p < TRr; p += NTT) sflag[p] = 0;
+  int* sflag = reinterpret_cast<int*>(lds + c.flg);  // (as conv_tile_f32)
+  for (int p = tid; p < TRr; p += NTA) sflag[p] = 0;
   // Z = A X for the tile's rows: 8 lanes per row, 4 bf16 (8 bytes) per lane
   // and edge, summed in fp32 in CSR order; rounded to bf16 once per row.
   const int nch = XSB >> 2, sub = tid & 7;
@@ -1961,16 +1760,16 @@ __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) 
     uint16_t* sXh = reinterpret_cast<uint16_t*>(lds + c.xh);
     const int h0 = pl.halo_off[tile], H = pl.halo_off[tile + 1] - h0;
     const int l0 = pl.lcol_off[tile];
-    drk::dma_words<NTT>(strp, s.rowptr + n0 + g + r0, nrows + 1);
-    drk::dma_words<NTT>(shid, pl.halo_ids + h0, H);
+    dma_copy<NTA, 4>(strp, s.rowptr + n0 + g + r0, nrows + 1);
+    dma_copy<NTA, 4>(shid, pl.halo_ids + h0, H);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     const int ebase = strp[0];
-    drk::dma_x4<NTT>(slcol, pl.lcol + l0, (strp[nrows] - ebase + 7) / 8);
+    dma_copy<NTA, 16>(slcol, pl.lcol + l0, (strp[nrows] - ebase + 7) / 8);
     {  // halo rows: 16-byte DMA lanes, XSB/8 per row
       const int n16 = XSB >> 3, tot = H * n16;
       const int wv = __builtin_amdgcn_readfirstlane(wave);
-      for (int base = wv * 64; base < tot; base += NTT)
+      for (int base = wv * 64; base < tot; base += NTA)
         if (base + lane < tot) {
           const int hr = (base + lane) / n16, q = base + lane - hr * n16;
           __builtin_amdgcn_global_load_lds(DRK_AS1(X + (int64_t)shid[hr] * XSB + q * 8), DRK_AS3(sXh + base * 8), 16, 0, 0);
@@ -1978,7 +1777,7 @@ __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) 
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    for (int r = tid >> 3; r < nrows; r += NTT / 8) {
+    for (int r = tid >> 3; r < nrows; r += NTA / 8) {
       const int eb = strp[r] - ebase, ee = strp[r + 1] - ebase;
       for (int ch = sub; ch < nch; ch += 8) {
         const int c4 = ch * 4;
@@ -1997,13 +1796,12 @@ __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) 
         for (; e < ee; ++e) acc = f4add(acc, unpack4bf(*reinterpret_cast<const uint2*>(&sXh[__umul24((int)slcol[e], XSB) + c4])));
         const uint2 zb = pack4bf(acc.x, acc.y, acc.z, acc.w);
         *reinterpret_cast<uint2*>(&sZ[r * ZSB + c4]) = zb;
-        if (!ZARGS) store_u64<INL>(zg + (int64_t)(r0 + r) * XSB + c4, (uint64_t)zb.x | ((uint64_t)zb.y << 32));
       }
     }
   } else {
     const int* rp = s.rowptr + n0 + g;
     const uint16_t* col = s.col + ec0;
-    for (int r = tid >> 3; r < nrows; r += NTT / 8) {
+    for (int r = tid >> 3; r < nrows; r += NTA / 8) {
       const int i = r0 + r;
       const int eb = rp[i], ee = rp[i + 1];
       for (int ch = sub; ch < nch; ch += 8) {
@@ -2021,17 +1819,15 @@ __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) 
         for (; e < ee; ++e) acc = f4add(acc, unpack4bf(*reinterpret_cast<const uint2*>(X + (int64_t)col[e] * XSB + c4)));
         const uint2 zb = pack4bf(acc.x, acc.y, acc.z, acc.w);
         *reinterpret_cast<uint2*>(&sZ[r * ZSB + c4]) = zb;
-        if (!ZARGS) store_u64<INL>(zg + (int64_t)i * XSB + c4, (uint64_t)zb.x | ((uint64_t)zb.y << 32));
       }
     }
   }
-  if (DR_TILE_STORE_WAIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (as in conv_tile_f32)
   __syncthreads();
   // H = relu(Z [W1; W1e]^T): lane l holds Z[row l&15][k 8(l>>4)..+7] and
   // W[col l&15][same k] (16-byte LDS reads); C row (l>>4)*4+r, col l&15.
   {
     const int li = lane & 15, kq = lane >> 4;
-    for (int tt = wave; tt * 16 < nrows; tt += NTT / 64) {
+    for (int tt = wave; tt * 16 < nrows; tt += NTA / 64) {
       const int q0 = tt * 16;
       const int ar = min(q0 + li, nrows - 1);
       floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -2052,20 +1848,17 @@ __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) 
       }
     }
   }
-  tile_partial_max<NTT, INL>(pl, sH, sm0i, sm0p, srng, compact, tile, b, K0, N, r0, nrows, ZARGS ? sflag : nullptr);
-  if (ZARGS) {
-    __syncthreads();
-    const int nch = XSB >> 2;
-    for (int p = tid; p < nrows * nch; p += NTT) {
-      const int r = p / nch, c4 = (p - r * nch) * 4;
-      if (sflag[r]) *reinterpret_cast<uint2*>(zg + (int64_t)(r0 + r) * XSB + c4) = *reinterpret_cast<const uint2*>(&sZ[r * ZSB + c4]);
-    }
+  tile_partial_max(pl, sH, sm0i, sm0p, srng, compact, tile, b, K0, N, r0, nrows, sflag);
+  __syncthreads();
+  for (int p = tid; p < nrows * nch; p += NTA) {
+    const int r = p / nch, c4 = (p - r * nch) * 4;
+    if (sflag[r]) *reinterpret_cast<uint2*>(zg + (int64_t)(r0 + r) * XSB + c4) = *reinterpret_cast<const uint2*>(&sZ[r * ZSB + c4]);
   }
 }
 
 __global__ void __launch_bounds__(NTA) ginet_large_conv1_bf16_kernel(LargeArgs la) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  conv_tile_bf16<NTA, false>(la, lds);
+  conv_tile_bf16(la, lds);
 }
 
 struct TailCarve {
@@ -2074,46 +1867,15 @@ struct TailCarve {
 
 __host__ __device__ inline TailCarve tail_carve(int K0, int P1, int K1, int alias, int OUT) {
   TailCarve c;
-  int o = 0;
-#define TAKE(field, words) \
-  {                        \
-    c.field = o;           \
-    o += r4(words);        \
-  }
-  TAKE(w2, 1024)
-  TAKE(fc2, OUT * 128 + OUT)
-  TAKE(p1, K0 * 32)
-  TAKE(a1, K0 * 32)
-  TAKE(dp1, K0 * 32)
-  TAKE(y2, K0 * 64)
-  TAKE(h2, K0 * 64)
-  TAKE(p1rp, K0 + 1)
-  TAKE(p1c, P1)
-  if (alias) {
-    c.p1trp = c.p1rp;
-    c.p1tc = c.p1c;
-  } else {
-    TAKE(p1trp, K0 + 1)
-    TAKE(p1tc, P1)
-  }
-  TAKE(m1p, K1 + 1)
-  TAKE(m1i, K0)
-  TAKE(p2, K1 * 64)
-  TAKE(nt, K1 * 64)
-  TAKE(cl1, K0)  // depth-1 cluster of each depth-0 cluster
-  TAKE(head, HEADW)
-  TAKE(dgp, NW * 64)
-#undef TAKE
-  c.total = o;
+  LdsWalk w;
+  take_head_weights(c, w, OUT);
+  take_tail_regions(c, w, K0, P1, K1, alias);
+  c.total = w.o;
   return c;
 }
 
-// One workgroup per graph: combine the tiles' partial maxima, then the tail.
-// The per-graph tail of the large path: combine the tiles' partial maxima,
-// then ginet_tail.  INL: run by the last-arriving tile workgroup of graph b
-// inside the one-launch kernel, so the tiles' hand-off (part_key atomics, Z
-// rows) is read with agent-scope (sc1) loads.
-template <bool INL>
+// The per-graph tail of the large path, one workgroup per graph: combine the
+// tiles' partial maxima, then ginet_tail.
 __device__ __forceinline__ void tail_body(const LargeArgs& la, int b, float* lds) {
   const GinetArgs& a = la.g;
   const dr_large_plan& pl = la.plan;
@@ -2133,14 +1895,14 @@ __device__ __forceinline__ void tail_body(const LargeArgs& la, int b, float* lds
   fc1_load(a.w, tid, tid >> 6, fc1_row, fc1_col, fc1_bias);
   const float y_g = s.y[g];
   uint64_t drop_offset = a.p.drop_offset;
-  drk::dma_words<NT>(t.p1rp, s.p1_rowptr + k00 + g, K0 + 1);
-  drk::dma_words<NT>(t.p1c, s.p1_col + q0, P1);
+  dma_copy<NT, 4>(t.p1rp, s.p1_rowptr + k00 + g, K0 + 1);
+  dma_copy<NT, 4>(t.p1c, s.p1_col + q0, P1);
   if (!alias) {
-    drk::dma_words<NT>(t.p1trp, s.p1t_rowptr + k00 + g, K0 + 1);
-    drk::dma_words<NT>(t.p1tc, s.p1t_col + q0, P1);
+    dma_copy<NT, 4>(t.p1trp, s.p1t_rowptr + k00 + g, K0 + 1);
+    dma_copy<NT, 4>(t.p1tc, s.p1t_col + q0, P1);
   }
-  drk::dma_words<NT>(t.m1p, s.m1_ptr + k10 + g, K1 + 1);
-  drk::dma_words<NT>(t.m1i, s.m1_idx + k00, K0);
+  dma_copy<NT, 4>(t.m1p, s.m1_ptr + k10 + g, K1 + 1);
+  dma_copy<NT, 4>(t.m1i, s.m1_idx + k00, K0);
   t.w2[tid] = (tid < 512) ? a.w.w2[tid] : a.w.w2e[tid - 512];
   for (int p = tid; p < OUT * 129; p += NT) t.fc2[p] = (p < OUT * 128) ? a.w.fc2w[p] : a.w.fc2b[p - OUT * 128];
   STAMP(1);
@@ -2149,14 +1911,8 @@ __device__ __forceinline__ void tail_body(const LargeArgs& la, int b, float* lds
   if (pl.part_key) {
     for (int p = tid; p < K0 * 32; p += NT) {
       unsigned long long* kp = reinterpret_cast<unsigned long long*>(pl.part_key) + (int64_t)b * pl.k0_max * 32 + p;
-      unsigned long long key;
-      if (INL) {
-        key = __hip_atomic_load((gu64*)(kp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store((gu64*)(kp), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else {
-        key = *kp;
-        *kp = 0ull;  // ready for the next pass
-      }
+      const unsigned long long key = *kp;
+      *kp = 0ull;  // ready for the next pass
       t.p1[p] = key ? __uint_as_float((uint32_t)(key >> 32)) : 0.f;
       t.a1[p] = key ? (int)(0xffffffffu - (uint32_t)key) : N;
     }
@@ -2203,30 +1959,19 @@ __device__ __forceinline__ void tail_body(const LargeArgs& la, int b, float* lds
   if (a.p.compute_dtype == DR_DTYPE_BF16) {  // the bf16 Z the conv1 GEMM consumed
     const int XSB = s.x_bf16_stride;
     const uint16_t* zb = reinterpret_cast<const uint16_t*>(pl.z) + (int64_t)pl.z_row0[b] * XSB;
-    if (INL)
-      ginet_tail(a, t, fc1_row, fc1_col, fc1_bias, row, N, K0, K1, F, OUT, y_g, drop_offset, [&](int i, int kk) {
-        const int64_t o = (int64_t)i * XSB + kk;  // the 4-byte word holding the bf16 value
-        const uint32_t w = load_sc1_u32(zb + (o & ~(int64_t)1));
-        return __uint_as_float((o & 1) ? (w & 0xffff0000u) : (w << 16));
-      }, -1);
-    else
-      ginet_tail(a, t, fc1_row, fc1_col, fc1_bias, row, N, K0, K1, F, OUT, y_g, drop_offset,
-                 [&](int i, int kk) { return bf2f(zb[(int64_t)i * XSB + kk]); }, -1);
+    ginet_tail(a, t, fc1_row, fc1_col, fc1_bias, row, N, K0, K1, F, OUT, y_g, drop_offset,
+               [&](int i, int kk) { return bf2f(zb[(int64_t)i * XSB + kk]); }, -1);
     return;
   }
   const float* z = pl.z + (int64_t)pl.z_row0[b] * r4(F);
   const int XS = r4(F);
-  if (INL)
-    ginet_tail(a, t, fc1_row, fc1_col, fc1_bias, row, N, K0, K1, F, OUT, y_g, drop_offset,
-               [&](int i, int kk) { return __uint_as_float(load_sc1_u32(z + (int64_t)i * XS + kk)); }, -1);
-  else
-    ginet_tail(a, t, fc1_row, fc1_col, fc1_bias, row, N, K0, K1, F, OUT, y_g, drop_offset,
-               [&](int i, int kk) { return z[(int64_t)i * XS + kk]; }, -1);
+  ginet_tail(a, t, fc1_row, fc1_col, fc1_bias, row, N, K0, K1, F, OUT, y_g, drop_offset,
+             [&](int i, int kk) { return z[(int64_t)i * XS + kk]; }, -1);
 }
 
 __global__ void __launch_bounds__(NT) ginet_large_tail_kernel(LargeArgs la) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  tail_body<false>(la, blockIdx.x, lds);
+  tail_body(la, blockIdx.x, lds);
 }
 
 }  // namespace
@@ -2246,12 +1991,19 @@ static int graph_pass_check(const dr_graph_store* store, const dr_graph_desc* de
   if (store->n_feat < 1 || 32 * store->n_feat > 2 * NT) return DR_E_UNSUPPORTED;  // F <= 64
   if (lds_bytes > 160 * 1024) return DR_E_LDS;
   if (pass->compute_dtype != DR_DTYPE_F32) return DR_E_UNSUPPORTED;  // bf16 runs dr_ginet_large_pass
-  if ((pass->flags & DR_PASS_BACKWARD) && (!pass->slab || !pass->head)) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_BACKWARD) && pass->loss_kind == DR_LOSS_NONE && !pass->dout) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_FORWARD) && !pass->out) return DR_E_ARG;
-  if (pass->use_dropout == DR_DROPOUT_MASK && !pass->mask) return DR_E_ARG;
-  if (pass->use_dropout < DR_DROPOUT_OFF || pass->use_dropout > DR_DROPOUT_HASH) return DR_E_ARG;
+  DR_CHECK(dr_check_pass_args(pass, true));
   return DR_OK;
+}
+
+// The per-graph kernels are instantiated for KPT = 32 (F <= 32) or 64 and for
+// the gather or the Z-input form: launch(KPT, ZIN) gets the two as
+// std::integral_constant values and returns the entry's result.
+template <class Launch>
+static int dispatch_kpt_zin(int F, bool zin, Launch launch) {
+  using K32 = std::integral_constant<int, 32>;
+  using K64 = std::integral_constant<int, 64>;
+  if (F <= 32) return zin ? launch(K32(), std::true_type()) : launch(K32(), std::false_type());
+  return zin ? launch(K64(), std::true_type()) : launch(K64(), std::false_type());
 }
 
 // dr_ginet_graph_pass (z = null) and dr_ginet_graph_pass_z
@@ -2269,20 +2021,12 @@ static int graph_pass_launch(const dr_graph_store* store, const dr_graph_desc* d
   args.B = n_batch;
   args.z = z;
   args.z_stride = z_stride;
-#define DR_GRAPH_LAUNCH(KPT, ZIN)                                                                                   \
-  do {                                                                                                              \
-    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_graph_kernel<KPT, ZIN>)));                       \
-    hipLaunchKernelGGL((ginet_graph_kernel<KPT, ZIN>), dim3(n_batch), dim3(NT), lds_bytes, (hipStream_t)stream, args); \
-  } while (0)
-  if (store->n_feat <= 32) {
-    if (z) DR_GRAPH_LAUNCH(32, true);
-    else DR_GRAPH_LAUNCH(32, false);
-  } else {
-    if (z) DR_GRAPH_LAUNCH(64, true);
-    else DR_GRAPH_LAUNCH(64, false);
-  }
-#undef DR_GRAPH_LAUNCH
-  return (int)hipGetLastError();
+  return dispatch_kpt_zin(store->n_feat, z != nullptr, [&](auto kpt, auto zin) {
+    const auto kernel = &ginet_graph_kernel<decltype(kpt)::value, decltype(zin)::value>;
+    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(kernel)));
+    hipLaunchKernelGGL(kernel, dim3(n_batch), dim3(NT), lds_bytes, (hipStream_t)stream, args);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int dr_ginet_graph_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
@@ -2341,21 +2085,12 @@ extern "C" int dr_ginet_input_grad_pass(const dr_graph_store* store, const dr_gr
   args.z = z;
   args.z_stride = z ? z_stride : 0;
   const dr_input_grad iga = *ig;
-#define DR_IG_LAUNCH(KPT, ZIN)                                                                                  \
-  do {                                                                                                          \
-    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_input_grad_kernel<KPT, ZIN>)));              \
-    hipLaunchKernelGGL((ginet_input_grad_kernel<KPT, ZIN>), dim3(n_batch), dim3(NT), lds_bytes,                 \
-                       (hipStream_t)stream, args, iga);                                                         \
-  } while (0)
-  if (store->n_feat <= 32) {
-    if (z) DR_IG_LAUNCH(32, true);
-    else DR_IG_LAUNCH(32, false);
-  } else {
-    if (z) DR_IG_LAUNCH(64, true);
-    else DR_IG_LAUNCH(64, false);
-  }
-#undef DR_IG_LAUNCH
-  return (int)hipGetLastError();
+  return dispatch_kpt_zin(store->n_feat, z != nullptr, [&](auto kpt, auto zin) {
+    const auto kernel = &ginet_input_grad_kernel<decltype(kpt)::value, decltype(zin)::value>;
+    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(kernel)));
+    hipLaunchKernelGGL(kernel, dim3(n_batch), dim3(NT), lds_bytes, (hipStream_t)stream, args, iga);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int dr_ginet_multi_pass(const dr_graph_store* store, const dr_ginet_member* members, int32_t n_members,
@@ -2384,21 +2119,12 @@ extern "C" int dr_ginet_multi_pass(const dr_graph_store* store, const dr_ginet_m
     args.m[k].descs = members[k].descs;
     args.m[k].B = members[k].n_batch;
   }
-#define DR_MULTI_LAUNCH(KPT, ZIN)                                                                                  \
-  do {                                                                                                             \
-    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_multi_kernel<KPT, ZIN>)));                      \
-    hipLaunchKernelGGL((ginet_multi_kernel<KPT, ZIN>), dim3(max_b, n_members), dim3(NT), lds_bytes,                \
-                       (hipStream_t)stream, args);                                                                 \
-  } while (0)
-  if (store->n_feat <= 32) {
-    if (z) DR_MULTI_LAUNCH(32, true);
-    else DR_MULTI_LAUNCH(32, false);
-  } else {
-    if (z) DR_MULTI_LAUNCH(64, true);
-    else DR_MULTI_LAUNCH(64, false);
-  }
-#undef DR_MULTI_LAUNCH
-  return (int)hipGetLastError();
+  return dispatch_kpt_zin(store->n_feat, z != nullptr, [&](auto kpt, auto zin) {
+    const auto kernel = &ginet_multi_kernel<decltype(kpt)::value, decltype(zin)::value>;
+    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(kernel)));
+    hipLaunchKernelGGL(kernel, dim3(max_b, n_members), dim3(NT), lds_bytes, (hipStream_t)stream, args);
+    return (int)hipGetLastError();
+  });
 }
 
 // Accumulating pass: n_groups workgroups, graph gi on workgroup gi % n_groups
@@ -2409,11 +2135,19 @@ extern "C" int dr_ginet_multi_pass(const dr_graph_store* store, const dr_ginet_m
 // for dr_ginet_graph_pass) plus the accumulators.
 extern "C" int32_t dr_ginet_acc_row_floats(int32_t n_feat, int32_t out_dim) { return acc_row_floats(n_feat, out_dim); }
 
+// The accumulating kernels' dynamic LDS: the accumulators and the staged flag
+// (acc_front_bytes), then a graph carve or (acc_prefetch_bytes) the prefetch
+// layout L of the batch maxima, Z-input form for zs > 0.
+static int64_t acc_front_bytes(int F, int OUT) { return 4LL * (acc_words(F, OUT, F > 32) + 4); }
+static int64_t acc_prefetch_bytes(const int32_t* max_sizes, int F, int alias, int OUT, int zs, AccLayout* L) {
+  *L = acc_layout(max_sizes[0], max_sizes[1], F, max_sizes[2], max_sizes[3], max_sizes[4], alias, OUT, zs);
+  return acc_front_bytes(F, OUT) + 4LL * L->total;
+}
+
 extern "C" int64_t dr_ginet_acc_lds_bytes(const int32_t* max_sizes, int32_t n_feat, int32_t transpose_aliased, int32_t out_dim) {
   if (!max_sizes) return -1;
-  const AccLayout L = acc_layout(max_sizes[0], max_sizes[1], n_feat, max_sizes[2], max_sizes[3], max_sizes[4],
-                                 transpose_aliased, out_dim);
-  return 4LL * (acc_words(n_feat, out_dim, n_feat > 32) + 4 + L.total);
+  AccLayout L;
+  return acc_prefetch_bytes(max_sizes, n_feat, transpose_aliased, out_dim, 0, &L);
 }
 
 // dr_ginet_acc_pass (z = null) and dr_ginet_acc_pass_z.  Whether the pass can
@@ -2440,23 +2174,18 @@ static int acc_pass_launch(const dr_graph_store* store, const dr_graph_desc* des
   if (pass->use_dropout == DR_DROPOUT_MASK && !pass->mask) return DR_E_ARG;
   if (pass->use_dropout < DR_DROPOUT_OFF || pass->use_dropout > DR_DROPOUT_HASH) return DR_E_ARG;
   const int F = store->n_feat, OUT = pass->out_dim;
-  const int64_t lds = (int64_t)lds_bytes + 4LL * (acc_words(F, OUT, F > 32) + 4);
+  const int64_t lds = (int64_t)lds_bytes + acc_front_bytes(F, OUT);
   AccLayout L{};
-  int64_t lds_pf = -1;
-  if (max_sizes) {
-    L = acc_layout(max_sizes[0], max_sizes[1], F, max_sizes[2], max_sizes[3], max_sizes[4], store->transpose_aliased, OUT);
-    lds_pf = dr_ginet_acc_lds_bytes(max_sizes, F, store->transpose_aliased, OUT);
-  }
+  const int64_t lds_pf = max_sizes ? acc_prefetch_bytes(max_sizes, F, store->transpose_aliased, OUT, 0, &L) : -1;
   const bool pf = lds_pf > 0 && lds_pf <= 160 * 1024;
   if (!pf && lds > 160 * 1024) return DR_E_LDS;
   int64_t lds_z = 0, lds_pf_z = 0;
   bool pf_z = false;
   if (z) {
-    lds_z = (int64_t)lds_z_bytes + 4LL * (acc_words(F, OUT, F > 32) + 4);
+    lds_z = (int64_t)lds_z_bytes + acc_front_bytes(F, OUT);
     if (pf) {
-      const AccLayout Lz = acc_layout(max_sizes[0], max_sizes[1], F, max_sizes[2], max_sizes[3], max_sizes[4],
-                                      store->transpose_aliased, OUT, z_stride);
-      lds_pf_z = 4LL * (acc_words(F, OUT, F > 32) + 4 + Lz.total);
+      AccLayout Lz;
+      lds_pf_z = acc_prefetch_bytes(max_sizes, F, store->transpose_aliased, OUT, z_stride, &Lz);
       pf_z = lds_pf_z <= 160 * 1024;
       if (pf_z) L = Lz;
     }
@@ -2473,24 +2202,16 @@ static int acc_pass_launch(const dr_graph_store* store, const dr_graph_desc* des
   args.B = n_batch;
   args.z = z;
   args.z_stride = z ? z_stride : 0;
-  const hipStream_t st = (hipStream_t)stream;
-#define DR_ACC_LAUNCH(KPT, PF, ZIN, BYTES)                                                                   \
-  do {                                                                                                     \
-    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_acc_kernel<KPT, PF, ZIN>)));            \
-    hipLaunchKernelGGL((ginet_acc_kernel<KPT, PF, ZIN>), dim3(n_groups), dim3(NT), (int)(BYTES), st, args, plan, L); \
-  } while (0)
-#define DR_ACC_PICK(KPT)                                 \
-  do {                                                   \
-    if (z && pf_z) DR_ACC_LAUNCH(KPT, true, true, lds_pf_z); \
-    else if (z) DR_ACC_LAUNCH(KPT, false, true, lds_z);  \
-    else if (pf) DR_ACC_LAUNCH(KPT, true, false, lds_pf); \
-    else DR_ACC_LAUNCH(KPT, false, false, lds);          \
-  } while (0)
-  if (F <= 32) DR_ACC_PICK(32);
-  else DR_ACC_PICK(64);
-#undef DR_ACC_PICK
-#undef DR_ACC_LAUNCH
-  return (int)hipGetLastError();
+  return dispatch_kpt_zin(F, z != nullptr, [&](auto kpt, auto zin) {
+    constexpr int KPT = decltype(kpt)::value;
+    constexpr bool ZIN = decltype(zin)::value;
+    const bool prefetch = ZIN ? pf_z : pf;
+    const int64_t bytes = ZIN ? (pf_z ? lds_pf_z : lds_z) : (pf ? lds_pf : lds);
+    const auto kernel = prefetch ? &ginet_acc_kernel<KPT, true, ZIN> : &ginet_acc_kernel<KPT, false, ZIN>;
+    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(kernel)));
+    hipLaunchKernelGGL(kernel, dim3(n_groups), dim3(NT), (int)bytes, (hipStream_t)stream, args, plan, L);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int dr_ginet_acc_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
@@ -2574,11 +2295,7 @@ extern "C" int dr_ginet_large_pass(const dr_graph_store* store, const dr_graph_d
     return DR_E_ARG;
   if (!plan->halo_ids && plan->halo_max) return DR_E_ARG;
   if (plan->arrive) return DR_E_ARG;  // (the one-launch form was removed in r06)
-  if ((pass->flags & DR_PASS_BACKWARD) && (!pass->slab || !pass->head)) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_BACKWARD) && pass->loss_kind == DR_LOSS_NONE && !pass->dout) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_FORWARD) && !pass->out) return DR_E_ARG;
-  if (pass->use_dropout == DR_DROPOUT_MASK && !pass->mask) return DR_E_ARG;
-  if (pass->use_dropout < DR_DROPOUT_OFF || pass->use_dropout > DR_DROPOUT_HASH) return DR_E_ARG;
+  DR_CHECK(dr_check_pass_args(pass, true));
   const bool bf16 = pass->compute_dtype == DR_DTYPE_BF16;
   if (pass->compute_dtype != DR_DTYPE_F32 && !bf16) return DR_E_ARG;
   if (bf16 && (!store->x_bf16 || store->x_bf16_stride < store->n_feat || store->x_bf16_stride % 8)) return DR_E_ARG;
@@ -2609,9 +2326,7 @@ extern "C" int dr_dropout_mask(uint64_t seed, uint64_t offset, int32_t n, float 
 }
 
 // ---- carve descriptions for the host-side carve tests (tests/test_lds_carves.py)
-extern "C" int dr_debug_carve_ginet(const int32_t* q, char* buf, int32_t len) {
-  const Carve c = carve(q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]);
-  DrCarveDesc d{buf, len, 0};
+static void describe_carve(DrCarveDesc& d, const Carve& c) {
   DR_DESC_P(d, c, KP);
   DR_DESC_P(d, c, LDW);
   DR_DESC_P(d, c, XS);
@@ -2641,7 +2356,55 @@ extern "C" int dr_debug_carve_ginet(const int32_t* q, char* buf, int32_t len) {
   DR_DESC(d, c, head);
   DR_DESC(d, c, dgp);
   DR_DESC(d, c, keep);
+}
+
+// q: N, E, F, K0, P1, K1, alias, OUT
+extern "C" int dr_debug_carve_ginet(const int32_t* q, char* buf, int32_t len) {
+  const Carve c = carve(q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]);
+  DrCarveDesc d{buf, len, 0};
+  describe_carve(d, c);
   DR_DESC(d, c, total);
+  return d.pos;
+}
+
+// the Z-input form; q: N, E, F, K0, P1, K1, alias, OUT, zs (> 0)
+extern "C" int dr_debug_carve_ginet_z(const int32_t* q, char* buf, int32_t len) {
+  const Carve c = carve(q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
+  DrCarveDesc d{buf, len, 0};
+  describe_carve(d, c);
+  DR_DESC(d, c, total);
+  return d.pos;
+}
+
+// The prefetch layout of the batch maxima and one graph's carve inside it.
+// q: N, E, F, K0, P1, K1, alias, OUT, then the maxima Nm, Em, K0m, P1m, K1m,
+// the parity and zs (0: gather form).  "total": the layout's; "$end": where
+// the graph's own walk of the scratch segment ends.
+extern "C" int dr_debug_carve_ginet_acc(const int32_t* q, char* buf, int32_t len) {
+  const AccLayout L = acc_layout(q[8], q[9], q[2], q[10], q[11], q[12], q[6], q[7], q[14]);
+  const Carve c = carve_acc(q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], L, q[13], q[14]);
+  DrCarveDesc d{buf, len, 0};
+  describe_carve(d, c);
+  dr_carve_put(d, "$in0", L.in0);
+  dr_carve_put(d, "$in1", L.in1);
+  dr_carve_put(d, "$scr", L.scr);
+  dr_carve_put(d, "$end", c.total);
+  dr_carve_put(d, "$acc_words", acc_words(q[2], q[7], q[2] > 32));
+  DR_DESC(d, L, total);
+  return d.pos;
+}
+
+// the input-gradient kernel's LDS: the per-graph carve and the transposed CSR;
+// q: N, E, F, K0, P1, K1, alias, OUT, zs (0: gather form)
+extern "C" int dr_debug_carve_ginet_ig(const int32_t* q, char* buf, int32_t len) {
+  const Carve c = carve(q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
+  const IgLds g = ig_lds(c, q[0], q[1], q[8]);
+  DrCarveDesc d{buf, len, 0};
+  describe_carve(d, c);
+  DR_DESC(d, g, trp);
+  DR_DESC(d, g, tcol);
+  dr_carve_put(d, "$carve_total", c.total);
+  DR_DESC(d, g, total);
   return d.pos;
 }
 
@@ -2730,7 +2493,7 @@ constexpr int WEIGHT_REGS_STRIDE = 49;  // per thread: fc1_row 8 | fc1_col 8 | f
 template <int KPT>
 __global__ void __launch_bounds__(NT) ginet_weight_regs_kernel(dr_ginet_weights w, int F, float* out) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr bool IMG = DR_W1_IMAGE && KPT == 32;
+  constexpr bool IMG = KPT == 32;
   constexpr int NKV = KPT / 4;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float* sW1 = lds;

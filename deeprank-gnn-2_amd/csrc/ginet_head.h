@@ -49,20 +49,10 @@ __device__ __forceinline__ void head_stamp(int64_t* row, int i) {
 #endif
 }
 
-// Per-graph partial stores: plain, or write-through (sc1: agent-scope relaxed
-// atomic stores) when other workgroups of the same launch read them
-// (dr_ginet_train_step's in-launch reduction; MI355X_MICROARCH.md
-// §inter-workgroup visibility).
-template <bool WT>
-__device__ __forceinline__ void st_part(float* p, float v) {
-  if (WT)
-    __hip_atomic_store((__attribute__((address_space(1))) unsigned int*)(p), __float_as_uint(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  else
-    *p = v;
-}
+// a per-graph partial's store
+__device__ __forceinline__ void st_part(float* p, float v) { *p = v; }
 
-template <int NT, bool WT = false, bool ACC = false>
+template <int NT, bool ACC = false>
 __device__ __forceinline__ bool ginet_head(const dr_pass& p, const GinetHeadLds& t, const float (&fc1_row)[8],
                                            const float (&fc1_col)[8], float fc1_bias, int b, int OUT, float y_g,
                                            uint64_t drop_offset, int stamp0 = -1, int pb = -1) {
@@ -105,7 +95,7 @@ __device__ __forceinline__ bool ginet_head(const dr_pass& p, const GinetHeadLds&
       if (tid == 0) {
         if (p.flags & DR_PASS_FORWARD) p.out[b] = logit;
         if (ACC) t.acc[128 + 128 + 1] += d * d;
-        else if (p.loss_per_graph) st_part<WT>(p.loss_per_graph + pb, d * d);
+        else if (p.loss_per_graph) st_part(p.loss_per_graph + pb, d * d);
         t.dout[0] = dout0;
       }
       head_stamp(srow, stamp0);
@@ -135,7 +125,7 @@ __device__ __forceinline__ bool ginet_head(const dr_pass& p, const GinetHeadLds&
       if (p.loss_kind == DR_LOSS_MSE) {
         const float d = t.dout[0] - y_g;
         if (ACC) t.acc[128 + 128 * OUT + OUT] += d * d;
-        else if (p.loss_per_graph) st_part<WT>(p.loss_per_graph + pb, d * d);
+        else if (p.loss_per_graph) st_part(p.loss_per_graph + pb, d * d);
         t.dout[0] = 2.f * d * p.loss_scale;
         for (int q = 1; q < OUT; ++q) t.dout[q] = 0.f;  // the loss reads column 0 only (engine's layer path alike)
       } else if (p.loss_kind == DR_LOSS_CE) {
@@ -147,13 +137,13 @@ __device__ __forceinline__ bool ginet_head(const dr_pass& p, const GinetHeadLds&
         const float lse = mx + logf(se);
         const float wy = p.class_w ? p.class_w[yi] : 1.f;
         if (ACC) t.acc[128 + 128 * OUT + OUT] += wy * (lse - t.dout[yi]);
-        else if (p.loss_per_graph) st_part<WT>(p.loss_per_graph + pb, wy * (lse - t.dout[yi]));
+        else if (p.loss_per_graph) st_part(p.loss_per_graph + pb, wy * (lse - t.dout[yi]));
         for (int q = 0; q < OUT; ++q) t.dout[q] = wy * (expf(t.dout[q] - lse) - (q == yi ? 1.f : 0.f)) * p.loss_scale;
       } else if (p.loss_kind != DR_LOSS_NONE) {  // L1 / SmoothL1 / Huber on column 0, as MSE
         float term, gd;
         dr_regress_loss(p.loss_kind, p.loss_param, t.dout[0] - y_g, &term, &gd);
         if (ACC) t.acc[128 + 128 * OUT + OUT] += term;
-        else if (p.loss_per_graph) st_part<WT>(p.loss_per_graph + pb, term);
+        else if (p.loss_per_graph) st_part(p.loss_per_graph + pb, term);
         t.dout[0] = gd * p.loss_scale;
         for (int q = 1; q < OUT; ++q) t.dout[q] = 0.f;
       } else {
@@ -214,12 +204,12 @@ __device__ __forceinline__ bool ginet_head(const dr_pass& p, const GinetHeadLds&
   } else {
     const int HS = DR_HEAD_STRIDE(OUT);
     float* hg = p.head + (int64_t)pb * HS;
-    if (tid < 64) st_part<WT>(hg + tid, t.g[tid]);
+    if (tid < 64) st_part(hg + tid, t.g[tid]);
     if (tid < 128) {
-      st_part<WT>(hg + 64 + tid, t.hd[tid]);
-      st_part<WT>(hg + 192 + tid, t.dh[tid]);
+      st_part(hg + 64 + tid, t.hd[tid]);
+      st_part(hg + 192 + tid, t.dh[tid]);
     }
-    if (tid < OUT) st_part<WT>(hg + 320 + tid, t.dout[tid]);
+    if (tid < OUT) st_part(hg + 320 + tid, t.dout[tid]);
   }
   if (!t.dg_deferred) __syncthreads();
 

@@ -156,11 +156,11 @@ __global__ void __launch_bounds__(NT) ginet_nocluster_kernel(NcArgs a) {
   }
   const float y_g = s.y[g];
   uint64_t drop_offset = a.p.drop_offset;
-  dma_x4<NT>(sX, s.x + n0 * (int64_t)XS, N * XS / 4);
-  dma_x4<NT>(scol, s.col + ec0, (E + 7) / 8);
-  dma_x4<NT>(stcol, s.t_col + ec0, (E + 7) / 8);
-  dma_words<NT>(srp, s.rowptr + n0 + g, N + 1);
-  dma_words<NT>(strp, s.t_rowptr + n0 + g, N + 1);
+  dma_copy<NT, 16>(sX, s.x + n0 * (int64_t)XS, N * XS / 4);
+  dma_copy<NT, 16>(scol, s.col + ec0, (E + 7) / 8);
+  dma_copy<NT, 16>(stcol, s.t_col + ec0, (E + 7) / 8);
+  dma_copy<NT, 4>(srp, s.rowptr + n0 + g, N + 1);
+  dma_copy<NT, 4>(strp, s.t_rowptr + n0 + g, N + 1);
   {
     const int padw = KP - F;
     for (int p = tid; p < 32 * padw; p += NT) {
@@ -871,11 +871,7 @@ extern "C" int dr_ginet_nocluster_graph_pass(const dr_graph_store* store, const 
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
   if (store->n_feat < 1 || 32 * store->n_feat > 2 * NT) return DR_E_UNSUPPORTED;  // F <= 64
   if (lds_bytes > 160 * 1024) return DR_E_LDS;
-  if ((pass->flags & DR_PASS_BACKWARD) && (!pass->slab || !pass->head)) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_BACKWARD) && pass->loss_kind == DR_LOSS_NONE && !pass->dout) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_FORWARD) && !pass->out) return DR_E_ARG;
-  if (pass->use_dropout == DR_DROPOUT_MASK && !pass->mask) return DR_E_ARG;
-  if (pass->use_dropout < DR_DROPOUT_OFF || pass->use_dropout > DR_DROPOUT_HASH) return DR_E_ARG;
+  DR_CHECK(dr_check_pass_args(pass, true));
   if (n_batch == 0) return DR_OK;
   DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_nocluster_kernel)));
   NcArgs args;
@@ -910,11 +906,7 @@ extern "C" int dr_ginet_nocluster_large_pass(const dr_graph_store* store, const 
       !plan->halo_ids || !plan->lcol_off || !plan->lcol || !plan->ltcol_off || !plan->ltcol ||
       plan->n_tiles < 1 || plan->halo_max < 1 || plan->halo_max > 65535)
     return DR_E_ARG;
-  if ((pass->flags & DR_PASS_BACKWARD) && (!pass->slab || !pass->head)) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_BACKWARD) && pass->loss_kind == DR_LOSS_NONE && !pass->dout) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_FORWARD) && !pass->out) return DR_E_ARG;
-  if (pass->use_dropout == DR_DROPOUT_MASK && !pass->mask) return DR_E_ARG;
-  if (pass->use_dropout < DR_DROPOUT_OFF || pass->use_dropout > DR_DROPOUT_HASH) return DR_E_ARG;
+  DR_CHECK(dr_check_pass_args(pass, true));
   const int64_t lds = dr_nc_large_lds_bytes(store->n_feat, plan->halo_max, plan->tile_edges_max, plan->tile_tedges_max, pass->out_dim);
   if (lds > 160 * 1024) return DR_E_LDS;
   if (n_batch == 0) return DR_OK;

@@ -3,19 +3,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/deeprank2_amd.h"
 #include "dr_common.h"
-
-#ifndef DR_GATHER_IMM
-#define DR_GATHER_IMM 1  // per-graph gathers: index reads as one base + immediate offsets (0: compiler-formed addresses)
-#endif
-
-#ifndef DR_Z_ARGS
-#define DR_Z_ARGS 1  // large-graph tile kernels: Z rows stored only at the tile's depth-0 pooling arg candidates (0: every row)
-#endif
-#ifndef DR_TILE_XCD
-#define DR_TILE_XCD 1  // tile kernels: consecutive tiles on one XCD (0: tile = blockIdx.x)
-#endif
 
 namespace drk {
 
@@ -35,27 +26,60 @@ __device__ __forceinline__ float relu_bwd(float out, float g) { return (out <= 0
 #define DRK_AS1(p) ((const __attribute__((address_space(1))) void*)(p))
 #define DRK_AS3(p) ((__attribute__((address_space(3))) void*)(p))
 
-// Asynchronous global->LDS copy of n 4-byte words (global_load_lds_dword: one
-// wave instruction moves 256 contiguous bytes).  M0 (the LDS base) is
-// wave-uniform; lane l lands at base + 4l.
-template <int NT>
-__device__ __forceinline__ void dma_words(void* lds_dst, const void* gsrc, int n) {
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t* src = reinterpret_cast<const uint32_t*>(gsrc);
-  uint32_t* dst = reinterpret_cast<uint32_t*>(lds_dst);
-  for (int base = wave * 64; base < n; base += NT)
-    if (base + lane < n) __builtin_amdgcn_global_load_lds(DRK_AS1(src + base + lane), DRK_AS3(dst + base), 4, 0, 0);
+// One LDS-DMA instruction from inline asm (M0 = the wave's LDS destination,
+// saved and restored around it: M0 is a reserved register the compiler may be
+// using)
+__device__ __forceinline__ void lds_dma_dword(uint32_t m0, const void* src) {
+  uint32_t saved;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(saved)
+               : "s"(m0), "v"(src));
+}
+__device__ __forceinline__ void lds_dma_x4(uint32_t m0, const void* src) {
+  uint32_t saved;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(saved)
+               : "s"(m0), "v"(src));
 }
 
-// 16-byte lanes (global_load_lds_dwordx4, 1 KiB per wave instruction); source
-// and destination 16-byte aligned; n4 = number of 16-byte units.
-template <int NT>
-__device__ __forceinline__ void dma_x4(void* lds_dst, const void* gsrc, int n4) {
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint4* src = reinterpret_cast<const uint4*>(gsrc);
-  uint4* dst = reinterpret_cast<uint4*>(lds_dst);
-  for (int base = wave * 64; base < n4; base += NT)
-    if (base + lane < n4) __builtin_amdgcn_global_load_lds(DRK_AS1(src + base + lane), DRK_AS3(dst + base), 16, 0, 0);
+// Asynchronous global->LDS copy of n lanes of BYTES bytes by the NT threads of
+// the workgroup, no VGPR round trip.  BYTES = 4: global_load_lds_dword, one
+// wave instruction moves 256 contiguous bytes; 16: global_load_lds_dwordx4,
+// 1 KiB, source and destination 16-byte aligned.  The LDS base handed to the
+// instruction (M0) is wave-uniform; lane l lands at base + BYTES * l.
+// ISSUE: DMA_BUILTIN, which the compiler waits for before the next LDS access,
+// or DMA_ASM (lds_dma_*): the compiler does not know these write LDS, so it
+// inserts no wait for them before later LDS reads and (no memory clobber)
+// reloads nothing around them -- for copies into LDS no one reads until an
+// explicit s_waitcnt vmcnt(0) + barrier.
+// w0, nw: the nw waves from wave w0 on (wrapping) take part, w0 the first 64
+// lanes (an LDS DMA instruction holds its wave ~a few hundred cycles at issue,
+// so the short copies of a staging sequence can start on different waves).
+enum DmaIssue { DMA_BUILTIN, DMA_ASM };
+template <int NT, int BYTES, DmaIssue ISSUE = DMA_BUILTIN>
+__device__ __forceinline__ void dma_copy(void* lds_dst, const void* gsrc, int n, int tid = threadIdx.x, int w0 = 0,
+                                         int nw = NT / 64) {
+  static_assert(BYTES == 4 || BYTES == 16, "dword or dwordx4 lanes");
+  static_assert((NT & (NT - 1)) == 0, "the wave index wraps by a mask");
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(w0 ? ((tid >> 6) - w0) & (NT / 64 - 1) : tid >> 6);
+  if (nw < NT / 64 && wave >= nw) return;
+  typedef typename std::conditional<BYTES == 16, uint4, uint32_t>::type unit;
+  const unit* src = reinterpret_cast<const unit*>(gsrc);
+  unit* dst = reinterpret_cast<unit*>(lds_dst);
+  const uint32_t dst_m0 = (uint32_t)(size_t)DRK_AS3(lds_dst);
+  for (int base = wave * 64; base < n; base += nw * 64)
+    if (base + lane < n) {
+      // (the builtin takes its size as a literal)
+      if (ISSUE == DMA_BUILTIN && BYTES == 16)
+        __builtin_amdgcn_global_load_lds(DRK_AS1(src + base + lane), DRK_AS3(dst + base), 16, 0, 0);
+      else if (ISSUE == DMA_BUILTIN)
+        __builtin_amdgcn_global_load_lds(DRK_AS1(src + base + lane), DRK_AS3(dst + base), 4, 0, 0);
+      else if (BYTES == 16)
+        lds_dma_x4(__builtin_amdgcn_readfirstlane(dst_m0 + 16 * base), src + base + lane);
+      else
+        lds_dma_dword(__builtin_amdgcn_readfirstlane(dst_m0 + 4 * base), src + base + lane);
+    }
 }
 
 // The tile a tile-kernel workgroup runs.  Workgroups are dispatched to the 8
@@ -64,7 +88,6 @@ __device__ __forceinline__ void dma_x4(void* lds_dst, const void* gsrc, int n4) 
 // graph's halo rows itself.  The bijective remap gives XCD group x the
 // contiguous tiles [x*per + min(x, rem), ...) (cdna_hip_programming.md T1).
 __host__ __device__ inline int xcd_tile_of(int b, int n) {
-  if (!DR_TILE_XCD) return b;
   const int x = b & 7, q = b >> 3, per = n >> 3, rem = n & 7;
   return x * per + (x < rem ? x : rem) + q;
 }
@@ -104,38 +127,6 @@ __device__ __forceinline__ float4 gather_row_chunk(const uint16_t* col, int eb, 
     acc = e + 2 < ee ? f4add(acc, v2) : acc;
   }
   return acc;
-}
-
-// One CSR row's sums of two 16-byte X chunks (c4a, c4b) at once: one index
-// read per edge feeds both chunks' row reads, four edges per step; each chunk
-// summed in edge order (same sums as gather_row_chunk)
-__device__ __forceinline__ void gather_row_two_chunks(const uint16_t* col, int eb, int ee, const float* X, int XS,
-                                                      int c4a, int c4b, float4& outa, float4& outb) {
-  float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-  int e = eb;
-  for (; e + 4 <= ee; e += 4) {
-    int e1 = e + 1, e2 = e + 2, e3 = e + 3;
-    asm volatile("" : "+v"(e1), "+v"(e2), "+v"(e3));
-    const int r0 = __umul24((int)col[e], XS), r1 = __umul24((int)col[e1], XS);
-    const int r2 = __umul24((int)col[e2], XS), r3 = __umul24((int)col[e3], XS);
-    const float4 v0 = *reinterpret_cast<const float4*>(&X[r0 + c4a]);
-    const float4 v1 = *reinterpret_cast<const float4*>(&X[r1 + c4a]);
-    const float4 v2 = *reinterpret_cast<const float4*>(&X[r2 + c4a]);
-    const float4 v3 = *reinterpret_cast<const float4*>(&X[r3 + c4a]);
-    const float4 w0 = *reinterpret_cast<const float4*>(&X[r0 + c4b]);
-    const float4 w1 = *reinterpret_cast<const float4*>(&X[r1 + c4b]);
-    const float4 w2 = *reinterpret_cast<const float4*>(&X[r2 + c4b]);
-    const float4 w3 = *reinterpret_cast<const float4*>(&X[r3 + c4b]);
-    a = f4add(f4add(f4add(f4add(a, v0), v1), v2), v3);
-    b = f4add(f4add(f4add(f4add(b, w0), w1), w2), w3);
-  }
-  for (; e < ee; ++e) {
-    const int r = __umul24((int)col[e], XS);
-    a = f4add(a, *reinterpret_cast<const float4*>(&X[r + c4a]));
-    b = f4add(b, *reinterpret_cast<const float4*>(&X[r + c4b]));
-  }
-  outa = a;
-  outb = b;
 }
 
 // The four index reads of a gather step from an LDS column array: one base
@@ -182,18 +173,15 @@ __device__ __forceinline__ float4 gather_row_chunk_imm(const uint16_t* col, int 
   return acc;
 }
 
-// gather_row_chunk for LDS column arrays: the _imm form unless built with
-// DR_GATHER_IMM=0 (A/B)
+// gather_row_chunk for LDS column arrays, in its arguments
 __device__ __forceinline__ float4 gather_row_chunk_lds(const uint16_t* col, int eb, int ee, const float* X, int XS, int c4) {
-#if DR_GATHER_IMM
   return gather_row_chunk_imm(col, eb, ee, reinterpret_cast<const char*>(X + c4), XS * 4);
-#else
-  return gather_row_chunk(col, eb, ee, X, XS, c4);
-#endif
 }
 
-// gather_row_two_chunks with fewer VALU instructions per edge, for the
-// per-graph kernels, whose gathers run 16 waves on 4 SIMDs and are VALU-issue
+// One CSR row's sums of two 16-byte X chunks at once: one index read per
+// edge feeds both chunks' row reads, four edges per step; each chunk summed in
+// edge order.  With few VALU instructions per edge, for the per-graph
+// kernels, whose gathers run 16 waves on 4 SIMDs and are VALU-issue
 // bound (a wave64 VALU op holds its SIMD 4 cycles): the four index reads of
 // a step are one base address and immediate offsets (inline asm, waited for
 // inside the same statement -- the compiler does not track them), and each

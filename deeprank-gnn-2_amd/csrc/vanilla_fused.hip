@@ -2078,10 +2078,10 @@ __global__ void __launch_bounds__(CT, 8) vc_eb2n1(VA a) {
   float* sX0 = lds + bc.x0;
   float* sS1 = lds + bc.s1;
   float* sW1 = lds + bc.w1;
-  dma_x4<CT>(sX1, ws + a.L.x1 + rt0 * XS, nr * XS / 4);
-  dma_x4<CT>(sDX, ws + a.L.dx1 + rt0 * XS, nr * XS / 4);
-  dma_x4<CT>(sX0, a.s.x + m.xrow * XS, nr * XS / 4);
-  dma_x4<CT>(sS1, ws + a.L.s1 + rt0 * 32, nr * 8);
+  dma_copy<CT, 16>(sX1, ws + a.L.x1 + rt0 * XS, nr * XS / 4);
+  dma_copy<CT, 16>(sDX, ws + a.L.dx1 + rt0 * XS, nr * XS / 4);
+  dma_copy<CT, 16>(sX0, a.s.x + m.xrow * XS, nr * XS / 4);
+  dma_copy<CT, 16>(sS1, ws + a.L.s1 + rt0 * 32, nr * 8);
   const Buf w1b(a.w.wn1, (int64_t)F * KN * 4);
   auto w1_off = [&](int p) -> int {  // vb_gemm<GM_DXS>'s W staging (Wn1), the DS columns
     const int k = p >> 5, n = p & 31;
@@ -2157,7 +2157,7 @@ __global__ void __launch_bounds__(CT, 8) vc_eb1(VA a) {
   __syncthreads();
   CSTAMP(4, 2);
   float* sX0 = lds + bc.x0;  // X0 rows into the dead edge space
-  dma_x4<CT>(sX0, a.s.x + m.xrow * XS, nr * XS / 4);
+  dma_copy<CT, 16>(sX0, a.s.x + m.xrow * XS, nr * XS / 4);
   #pragma unroll 1
   for (int p = tid; p < (WR - nr) * XS; p += CT) sX0[nr * XS + p] = 0.f;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

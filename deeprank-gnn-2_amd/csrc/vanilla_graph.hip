@@ -753,7 +753,7 @@ __global__ void __launch_bounds__(NT) vanilla_graph_kernel(VGArgs a) {
 
   VSTAMP(0);
   // ---------------- stage: CSR rows, edge records, X0 into LDS ------------
-  dma_words<NT>(srp, s.rowptr + d.node0 + g, N + 1);
+  dma_copy<NT, 4>(srp, s.rowptr + d.node0 + g, N + 1);
   {
     const uint16_t* gcol = s.col + d.col0;
     uint32_t* r32 = reinterpret_cast<uint32_t*>(rec);
@@ -833,8 +833,8 @@ __global__ void __launch_bounds__(NT) vanilla_graph_kernel(VGArgs a) {
   // land in U while the forward finishes
   if (bwd) {
     if (!split) gather_words(bt, bt2g, teid, 0, E);  // (split: after hand-off 2)
-    dma_words<NT>(strp, s.t_rowptr + d.node0 + g, N + 1);
-    dma_x4<NT>(stcol, s.t_col + d.col0, (E + 7) / 8);
+    dma_copy<NT, 4>(strp, s.t_rowptr + d.node0 + g, N + 1);
+    dma_copy<NT, 16>(stcol, s.t_col + d.col0, (E + 7) / 8);
   }
   // X2 = relu([X1 | S2] Wn2^T + bn2) -> P, own rows
   mm_w<2>(nown, [&](int i, int k) { return k < 32 ? Q[(r0 + i) * LS + k] : R[(r0 + i) * LS + k - 32]; },
@@ -1035,8 +1035,8 @@ __global__ void __launch_bounds__(NT) vanilla_graph_kernel(VGArgs a) {
   // ---------------- layer 1 backward ---------------------------------------
   // X0 (HBM row stride XS) -> Q, S1 -> R (stride 32), layer-1 ReLU words -> U:
   // bulk DMA (own rows), landing while dS1 = DU1 Wn1[:, F:] -> T runs
-  dma_x4<NT>(Q + r0 * XS, X0 + (int64_t)r0 * XS, nown * XS / 4);
-  dma_x4<NT>(R + r0 * 32, S1g + r0 * 32, nown * 8);
+  dma_copy<NT, 16>(Q + r0 * XS, X0 + (int64_t)r0 * XS, nown * XS / 4);
+  dma_copy<NT, 16>(R + r0 * 32, S1g + r0 * 32, nown * 8);
   gather_words(bt, bt1g, teid, strp[r0], strp[r1]);
   mm_w<1>(nown, [&](int i, int n) { return P[(r0 + i) * LS + n]; },
           a.wpack + op_base(OP_DS1), [&](int) -> const float* { return nullptr; },
@@ -1128,10 +1128,7 @@ extern "C" int dr_vanilla_fused_pass(const dr_graph_store* store, const dr_graph
   if (!store->t_eid || !store->t_rowptr || !store->t_col || (store->n_edge_feat > 0 && !store->ea)) return DR_E_ARG;
   if (lds_bytes > 160 * 1024) return DR_E_LDS;
   if (!scratch || !scratch_off) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_BACKWARD) && (!pass->slab || !pass->head)) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_BACKWARD) && pass->loss_kind == DR_LOSS_NONE && !pass->dout) return DR_E_ARG;
-  if ((pass->flags & DR_PASS_FORWARD) && !pass->out) return DR_E_ARG;
-  if (pass->use_dropout != DR_DROPOUT_OFF) return DR_E_UNSUPPORTED;
+  DR_CHECK(dr_check_pass_args(pass, false));
   if (n_batch == 0) return DR_OK;
   const void* fn = nullptr;
   switch (store->n_edge_feat) {

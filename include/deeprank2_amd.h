@@ -996,6 +996,18 @@ int dr_device_arch(char* buf, int32_t len); /* e.g. "gfx950"; 0 on success */
  * flag + limit bytes; conv / tail variants: their own orders, see the tests).
  * ---------------------------------------------------------------------- */
 int dr_debug_carve_ginet(const int32_t* q, char* buf, int32_t len);
+/* the Z-input form: q = dr_ginet_z_lds_bytes' arguments (.., out_dim, z_stride) */
+int dr_debug_carve_ginet_z(const int32_t* q, char* buf, int32_t len);
+/* The accumulating pass's prefetch layout and one graph's carve inside it:
+ * q = the graph's N, E, F, K0, P1, K1, transpose_aliased, out_dim, the batch
+ * maxima N, E, K0, P1, K1 (dr_ginet_acc_lds_bytes' max_sizes), the input
+ * buffer's parity, z_stride (0: gather form).  "$in0" / "$in1" / "$scr": the
+ * segment starts, "total": the layout's words, "$end": the end of the graph's
+ * own scratch walk, "$acc_words": the accumulators ahead of the carve. */
+int dr_debug_carve_ginet_acc(const int32_t* q, char* buf, int32_t len);
+/* dr_ginet_input_grad_lds_bytes' arguments: the per-graph carve, then the
+ * transposed CSR ("trp", "tcol"); "$carve_total": the carve's own words. */
+int dr_debug_carve_ginet_ig(const int32_t* q, char* buf, int32_t len);
 int dr_debug_carve_ginet_conv(const int32_t* q, char* buf, int32_t len);
 int dr_debug_carve_ginet_conv_bf16(const int32_t* q, char* buf, int32_t len);
 int dr_debug_carve_ginet_tail(const int32_t* q, char* buf, int32_t len);

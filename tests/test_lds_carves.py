@@ -135,6 +135,111 @@ def test_ginet_graph_carve(N, E, F, K0, P1, K1, alias, OUT):
     _check("ginet", q, _ginet_ext(*q), aliases=[("p1rp", "p1trp"), ("p1c", "p1tc")], host_bytes=_lib.load().dr_ginet_lds_bytes(*q))
 
 
+# ---- GINet Z-input form (carve(.., zs > 0); graph_body<.., ZIN>) ----
+GINET_GRAPHS = [(1, 0, 1, 0, 1, 1, 1), (30, 120, 3, 6, 1, 1, 2), (200, 3000, 5, 14, 1, 1, 1), (220, 4400, 6, 22, 2, 0, 16), (170, 11900, 1, 0, 1, 1, 2)]
+
+
+def _ginet_z_ext(N, E, F, K0, P1, K1, alias, OUT, zs):
+    """_ginet_ext with Z an input: rows of zs words, no x / rp / col."""
+
+    def ext(v):
+        KP = 32 if F <= 32 else 64
+        assert v["$LDW"] == zs >= KP
+        e = _ginet_ext(N, E, F, K0, P1, K1, alias, OUT)({**v, "$LDW": KP + 2})
+        return e | {"x": 0, "rp": 0, "col": 0, "z": N * zs}  # for_graph_inputs: N zs words or N zs / 4 16-byte lanes
+
+    return ext
+
+
+@pytest.mark.parametrize(("N", "E", "K0", "P1", "K1", "alias", "OUT"), GINET_GRAPHS)
+@pytest.mark.parametrize(("F", "zs"), [(F, KP + d) for F, KP in ((1, 32), (30, 32), (32, 32), (33, 64), (50, 64)) for d in (0, 2, 4)])
+def test_ginet_graph_carve_z_input(N, E, F, K0, P1, K1, alias, OUT, zs):
+    q = [N, E, F, K0, P1, K1, alias, OUT, zs]
+    vals, _ = _check("ginet_z", q, _ginet_z_ext(*q), aliases=[("p1rp", "p1trp"), ("p1c", "p1tc")], host_bytes=_lib.load().dr_ginet_z_lds_bytes(*q))
+    assert (vals["x"], vals["rp"], vals["col"]) == (0, 0, 0)  # not carved
+
+
+# ---- GINet input-gradient kernel (ig_lds: the carve and the transposed CSR) ----
+@pytest.mark.parametrize(("N", "E", "K0", "P1", "K1", "alias", "OUT"), GINET_GRAPHS)
+@pytest.mark.parametrize(("F", "zs"), [(1, 0), (30, 0), (50, 0), (1, 34), (30, 32), (30, 36), (50, 66)])
+def test_ginet_input_grad_lds(N, E, F, K0, P1, K1, alias, OUT, zs):
+    q = [N, E, F, K0, P1, K1, alias, OUT, zs]
+    base = _ginet_z_ext(*q) if zs else _ginet_ext(*q[:8])
+
+    def ext(v):
+        return base(v) | {"trp": N + 1, "tcol": ((E + 7) // 8) * 4}  # dma_copy of N + 1 words, (E + 7) / 8 16-byte units
+
+    aliases = [("p1rp", "p1trp"), ("p1c", "p1tc"), ("rp", "trp"), ("col", "tcol")]
+    vals, total = _check("ginet_ig", q, ext, aliases=aliases, host_bytes=_lib.load().dr_ginet_input_grad_lds_bytes(*q))
+    carve = _carve("ginet_z", q) if zs else _carve("ginet", q[:8])
+    assert vals["$carve_total"] == carve["total"]
+    assert all(vals[k] == o for k, o in carve.items() if k != "total")
+    if zs:  # appended after the carve: trp, then tcol
+        assert vals["trp"] == carve["total"]
+        assert vals["tcol"] == vals["trp"] + r4(N + 1)
+        assert total == vals["tcol"] + r4((E + 1) // 2)
+    else:  # the gather form's rp / col regions, dead after the front half
+        assert (vals["trp"], vals["tcol"], total) == (vals["rp"], vals["col"], carve["total"])
+
+
+# ---- GINet accumulating pass, prefetch layout (acc_layout / carve_acc; graph_body<.., PF>) ----
+def _acc_closed_form(Nm, Em, F, K0m, P1m, K1m, alias, OUT, zs):
+    """in0, in1, scr, total as the layout was first written: a closed-form sum."""
+    XS, LDW = r4(F), zs if zs else (32 if F <= 32 else 64) + 2
+    in0 = r4(32 * F) + 1024 + r4(OUT * 128 + OUT)
+    inputs = (r4(Nm * LDW) if zs else r4(Nm * XS) + r4(Nm + 1) + r4((Em + 1) // 2)) + r4(Nm) + r4(K0m + 1) + r4(P1m)
+    inputs += (0 if alias else r4(K0m + 1) + r4(P1m)) + r4(K1m + 1) + r4(K0m)
+    in1, scr = in0 + inputs, in0 + 2 * inputs
+    total = scr + (0 if zs else r4(Nm * LDW)) + r4(2 * K0m * 32) + 3 * r4(K0m * 32) + 2 * r4(K0m * 64) + 2 * r4(K1m * 64) + r4(K0m)
+    return in0, in1, scr, total + r4(672) + r4(16 * 64) + r4(32)
+
+
+ACC_WEIGHTS = ("w1", "w2", "fc2")
+ACC_INPUTS = ("x", "rp", "col", "cl0", "p1rp", "p1c", "p1trp", "p1tc", "m1p", "m1i")
+# a graph equal to the maxima in every size, with the smallest graph; maxima taken
+# from two graphs (largest N and K0 from one, largest E, P1 and K1 from the other)
+ACC_BATCHES = [
+    [(200, 3000, 5, 14, 2), (1, 0, 1, 0, 1)],
+    [(220, 1000, 6, 10, 1), (150, 4400, 4, 22, 3)],
+]
+
+
+@pytest.mark.parametrize("batch", ACC_BATCHES)
+@pytest.mark.parametrize("F", [1, 8, 30, 32, 33, 64])
+@pytest.mark.parametrize("dz", [None, 0, 2, 4])  # gather form, or Z rows of KPT + dz words
+@pytest.mark.parametrize("alias", [0, 1])
+@pytest.mark.parametrize("OUT", [1, 2, 16])
+def test_ginet_acc_prefetch_layout(batch, F, dz, alias, OUT):
+    lib = _lib.load()
+    zs = 0 if dz is None else (32 if F <= 32 else 64) + dz
+    maxima = [max(g[i] for g in batch) for i in range(5)]  # N, E, K0, P1, K1
+    Nm, Em, K0m, P1m, K1m = maxima
+    lay = _acc_closed_form(Nm, Em, F, K0m, P1m, K1m, alias, OUT, zs)
+    in0, in1, scr, total = lay
+    span = in1 - in0
+    assert in0 < in1 and in1 + span == scr < total  # two parities and the scratch, pairwise disjoint
+    acc_words = 32 * F + 1024 + r4(128 + 128 * OUT + OUT + 1) + (128 * 64 if F > 32 else 0)
+    if not zs:
+        assert 4 * (acc_words + 4 + total) == lib.dr_ginet_acc_lds_bytes((ctypes.c_int32 * 5)(*maxima), F, alias, OUT)
+    seg_inputs = ACC_INPUTS + (("z",) if zs else ())
+    for N, E, K0, P1, K1 in batch:
+        for par in (0, 1):
+            q = [N, E, F, K0, P1, K1, alias, OUT, *maxima, par, zs]
+            ext_of = _ginet_z_ext(N, E, F, K0, P1, K1, alias, OUT, zs) if zs else _ginet_ext(N, E, F, K0, P1, K1, alias, OUT)
+            vals, got_total = _check("ginet_acc", q, ext_of, aliases=[("p1rp", "p1trp"), ("p1c", "p1tc")])
+            assert (vals["$in0"], vals["$in1"], vals["$scr"], got_total) == lay, (q, lay)
+            assert vals["$acc_words"] == acc_words
+            assert scr <= vals["$end"] <= total  # the graph's own scratch walk ends inside the layout's
+            buf = in1 if par else in0
+            for k, need in ext_of(vals).items():
+                if not need:
+                    continue
+                o = vals[k]
+                assert o % 4 == 0, (q, k, o)
+                lo, hi = (0, in0) if k in ACC_WEIGHTS else (buf, buf + span) if k in seg_inputs else (scr, total)
+                assert lo <= o and o + need <= hi, f"ginet_acc{tuple(q)}: {k} [{o}, {o + need}) leaves its segment [{lo}, {hi})"
+
+
 # ---- GINet large-graph tile / tail kernels (ginet_fused.hip:990-1030, :1292-1330, :1479-1525) ----
 TR = 128  # DR_LARGE_TILE
 
