@@ -230,6 +230,8 @@ class ParamTableC(ctypes.Structure):
 DR_MAX_MEMBERS = 8
 DR_ENS_REGRESS = 0
 DR_ENS_CLASSIF = 1
+DR_SCORE_SUMS = 12
+DR_SCORE_PROBS = 1
 
 
 class GinetMemberC(ctypes.Structure):
@@ -269,6 +271,7 @@ SIGNATURES = [
     ("dr_reduce_multi_build", ctypes.c_int, [ctypes.POINTER(ReduceMemberC), ctypes.c_int32, VP, ctypes.c_int64]),
     ("dr_reduce_update_multi", ctypes.c_int, [VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, VP]),
     ("dr_ensemble_stats", ctypes.c_int, [VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, VP, VP, VP, VP]),
+    ("dr_ensemble_score", ctypes.c_int, [VP, ctypes.c_int64, VP, ctypes.c_int64, VP, ctypes.c_int64, _c_i32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, VP, ctypes.c_int32, VP, VP, VP]),
     ("dr_ginet_large_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(LargePlanC), ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, ctypes.c_int32, VP]),
     ("dr_ginet_large_conv_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 5),
     ("dr_ginet_nocluster_large_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(NcPlanC), ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), VP]),

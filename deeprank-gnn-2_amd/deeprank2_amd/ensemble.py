@@ -26,6 +26,17 @@ over their batches as grids (max B_k, K) of forward-only rows of the same
 HIP graph.  ``train_ensemble`` validates through it; ``predict_ensemble`` adds
 the ensemble's mean and spread (``dr_ensemble_stats``, one launch);
 ``out_of_fold_predictions`` gives a cross-validation's out-of-fold scores.
+
+Scores formed on the device: a runner built with a ``ScoreSpec`` ends its run
+(its captured graph) with one ``dr_ensemble_score`` launch, which turns the
+predictions, the staged graph ids and the store's targets into K rows of fp64
+sums in a fixed order; ``scores_from_sums`` makes the loss over the whole
+held-out set and the metrics (RMSE, MAE, Pearson r, R^2; accuracy, the
+confusion matrix and its binary rates) of them on the host.
+``train_ensemble(val_loss="device")`` validates that way, ``patience`` /
+``restore_best`` stop members early on the validation loss
+(``MemberStopping``), and ``score_ensemble`` scores the members and the
+ensemble's mean prediction.
 """
 
 from __future__ import annotations
@@ -267,6 +278,10 @@ class EnsembleResult:
     val_loss: np.ndarray | None  # [nepoch, K] held-out loss, or None without val_indices
     models: list
     val_path: str | None = None  # "fused" or "sequential": how the held-out graphs were evaluated (None without val_indices)
+    val_scores: list | None = None  # val_loss="device": the epochs' ``Scores`` of the held-out sets, one per epoch run
+    best_epoch: np.ndarray | None = None  # [K] int: the epoch of each member's lowest validation loss (-1: none; None without val_indices)
+    stopped_epoch: np.ndarray | None = None  # [K] int: the epoch after which patience stopped the member (-1: never)
+    step: FusedEnsembleStep | None = None  # the step that trained them: ``step.steps[k]`` holds member k's optimizer state and device counters
 
 
 def _store_of(dataset, device):
@@ -368,6 +383,250 @@ def _check_batches(sizes, batches, n_graphs=None):
     return out
 
 
+SCORE_SUMS = _lib.DR_SCORE_SUMS
+
+
+@dataclass
+class ScoreSpec:
+    """What a ``FusedEnsembleForward`` scores its predictions with
+    (``dr_ensemble_score`` as the run's last launch): the loss of the training
+    step (a key of ``LOSS_KINDS``), SmoothL1's beta / Huber's delta (default
+    1.0), the cross entropy's class weights, and whether the confusion matrix
+    is counted (cross entropy only)."""
+
+    loss: str
+    loss_param: float | None = None
+    class_weights: object = None
+    confusion: bool = False
+
+    def checked(self, out_dim):
+        """The spec with its defaults filled in, refused on the host as the C entry would."""
+        if self.loss not in LOSS_KINDS:
+            msg = f"loss must be one of {sorted(LOSS_KINDS)} (got {self.loss!r})"
+            raise ValueError(msg)
+        param = float(1.0 if self.loss_param is None else self.loss_param) if self.loss in ("smooth_l1", "huber") else 0.0
+        if not (param >= 0.0 and param != float("inf")) or (self.loss == "huber" and param == 0.0):
+            msg = f"loss_param must be a finite beta >= 0 (smooth_l1) or delta > 0 (huber) (got {self.loss_param!r})"
+            raise ValueError(msg)
+        if self.loss == "ce" and out_dim < 2:
+            msg = "the cross entropy needs at least two outputs"
+            raise ValueError(msg)
+        if self.loss != "ce" and self.confusion:
+            msg = "a confusion matrix is counted for the cross entropy only"
+            raise ValueError(msg)
+        return ScoreSpec(self.loss, param, self.class_weights if self.loss == "ce" else None, bool(self.confusion))
+
+    @property
+    def task(self):
+        return "classif" if self.loss == "ce" else "regress"
+
+
+class _ScoreLaunch:
+    """One ``dr_ensemble_score`` over fixed buffers: ``out`` [K, rows, out_dim]
+    against ``y[gids]`` (``gids`` [K, rows] or [rows] int64, or None: ``y[i]``),
+    member k's first ``n[k]`` rows.  The output buffers are made here (or
+    taken); calling the object makes the launch, nothing else, so it can be
+    captured."""
+
+    def __init__(self, out, y, gids, n, spec: ScoreSpec, probs, sums=None, confusion=None):
+        _lib.require_device(out, y, gids)
+        if out.dim() != 3 or out.dtype != torch.float32 or out.stride(2) != 1 or out.stride(1) != out.shape[2]:
+            msg = "out must be fp32 [K, n, out] with contiguous [n, out] blocks"
+            raise ValueError(msg)
+        k, rows, out_dim = out.shape
+        spec = spec.checked(out_dim)
+        if probs and spec.loss != "ce":
+            msg = "probs goes with the cross entropy only"
+            raise ValueError(msg)
+        if y.dim() != 1 or y.dtype != torch.float32 or not y.is_contiguous():
+            msg = "y must be a contiguous fp32 vector (the store's targets)"
+            raise ValueError(msg)
+        n = [rows] * k if n is None else [int(v) for v in n]
+        if len(n) != k or any(v < 0 or v > rows for v in n):
+            msg = f"n needs one row count in 0..{rows} per member ({k})"
+            raise ValueError(msg)
+        gid_stride = 0
+        if gids is not None:
+            if gids.dtype != torch.int64 or gids.dim() not in (1, 2) or gids.stride(-1) != 1 or gids.shape[-1] < max(n):
+                msg = "gids must be int64 [n] or [K, n] with contiguous rows of at least max(n) ids"
+                raise ValueError(msg)
+            if gids.dim() == 2:
+                if gids.shape[0] != k:
+                    msg = f"gids has {gids.shape[0]} rows for {k} members"
+                    raise ValueError(msg)
+                gid_stride = gids.stride(0) if k > 1 else 0
+        elif max(n) > y.numel():
+            msg = "without gids row i scores against y[i]: more rows than targets"
+            raise ValueError(msg)
+        cw = spec.class_weights
+        if cw is not None:
+            cw = torch.as_tensor(cw, dtype=torch.float32, device=out.device).contiguous()
+            if cw.numel() != out_dim:
+                msg = f"class_weights needs {out_dim} entries (got {cw.numel()})"
+                raise ValueError(msg)
+        self.out, self.y, self.gids, self.n, self.spec, self.class_w = out, y, gids, n, spec, cw
+        self.gid_stride = gid_stride
+        self.flags = _lib.DR_SCORE_PROBS if probs else 0
+        self._n = (ctypes.c_int32 * k)(*n)
+        dev = out.device
+        with torch.cuda.device(dev):
+            self.sums = torch.zeros(k, SCORE_SUMS, dtype=torch.float64, device=dev) if sums is None else sums
+            self.confusion = (torch.zeros(k, out_dim, out_dim, dtype=torch.int64, device=dev) if confusion is None else confusion) if spec.confusion else None
+
+    def __call__(self):
+        k, _, out_dim = self.out.shape
+        rc = _lib.load().dr_ensemble_score(self.out.data_ptr(), self.out.stride(0), _lib.ptr(self.gids), self.gid_stride, self.y.data_ptr(), self.y.numel(), self._n, k, out_dim,
+                                           LOSS_KINDS[self.spec.loss], self.spec.loss_param, _lib.ptr(self.class_w), self.flags, self.sums.data_ptr(), _lib.ptr(self.confusion),
+                                           _lib.stream_ptr(self.out.device))  # fmt: skip
+        _lib.check(rc, "dr_ensemble_score")
+
+
+def ensemble_score(out, y, *, gids=None, n=None, loss, loss_param=None, class_weights=None, probs=False, confusion=False):
+    """``dr_ensemble_score`` on ``out`` [K, rows, out] (fp32, on the device; a
+    view whose members are more than rows * out floats apart is fine; [rows,
+    out] is one member) against the targets ``y`` (fp32 device vector, the
+    store's ``y``): member k's row i scores against ``y[gids[k, i]]`` (``gids``
+    int64 on the device, [K, rows], or [rows] for all members), or ``y[i]``
+    without ``gids``; ``n[k]`` (default: all) rows of member k are scored.
+    ``loss``: a key of ``LOSS_KINDS``; ``probs``: ``out`` holds probabilities
+    (cross entropy: the term is -log p_y).  Returns ``(sums [K, 12] float64 on
+    the device, confusion [K, out, out] int64 or None)``; ``scores_from_sums``
+    turns them into metrics on the host."""
+    if out.dim() == 2:
+        out = out.unsqueeze(0)
+    launch_ = _ScoreLaunch(out, y, gids, n, ScoreSpec(loss, loss_param, class_weights, confusion), probs)
+    with torch.cuda.device(out.device):
+        launch_()
+    return launch_.sums, launch_.confusion
+
+
+@dataclass
+class Scores:
+    """Per-member metrics (arrays [K]) from the sums of ``dr_ensemble_score``;
+    a field that does not apply to the task is None."""
+
+    loss: np.ndarray  # the loss over the whole scored set: slot 0 / slot 1 (NaN when slot 1 is 0)
+    n: np.ndarray  # rows scored (int64)
+    n_nan: np.ndarray  # of those, rows with a NaN term (regression) or a NaN logit (classification)
+    n_skipped: np.ndarray  # rows left out: id outside the store, or a target that is no class index
+    rmse: np.ndarray | None = None
+    mae: np.ndarray | None = None
+    pearson: np.ndarray | None = None
+    r2: np.ndarray | None = None
+    accuracy: np.ndarray | None = None
+    confusion: np.ndarray | None = None  # [K, C, C] int64, row = target, column = predicted
+    mcc: np.ndarray | None = None
+    tpr: np.ndarray | None = None
+    tnr: np.ndarray | None = None
+    precision: np.ndarray | None = None
+
+
+def _ratio(num, den):
+    """num / den, NaN where den is 0 (or not finite arithmetic: no exception, no warning)."""
+    num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        return np.where(den == 0, np.nan, num / np.where(den == 0, 1.0, den))
+
+
+def scores_from_sums(sums, confusion, task):
+    """Metrics from ``dr_ensemble_score``'s sums S [K, 12] (numpy, float64) and
+    optional confusion matrices [K, C, C]; pure host arithmetic in float64.
+    A zero denominator gives NaN.
+
+    Always: ``loss = S0 / S1``, ``n_nan = S2``, ``n_skipped = S3``.
+
+    ``task = "regress"`` (n = S1, d = o - y; S4 = sum d^2, S5 = sum |d|, S6 =
+    sum o, S7 = sum y, S8 = sum o^2, S9 = sum y^2, S10 = sum o y)::
+
+        rmse    = sqrt(S4 / n)
+        mae     = S5 / n
+        pearson = (n S10 - S6 S7) / sqrt((n S8 - S6^2) (n S9 - S7^2))
+        r2      = 1 - S4 / (S9 - S7^2 / n)
+
+    ``task = "classif"`` (n = S5, the rows scored; S1 is the sum of the class
+    weights): ``accuracy = S4 / n``.  With a confusion matrix M (row = target,
+    column = predicted) it is returned, and for two classes, with tn = M00,
+    fp = M01, fn = M10, tp = M11::
+
+        tpr       = tp / (tp + fn)
+        tnr       = tn / (tn + fp)
+        precision = tp / (tp + fp)
+        mcc       = (tp tn - fp fn) / sqrt((tp + fp) (tp + fn) (tn + fp) (tn + fn))
+    """
+    if task not in ENS_KINDS:
+        msg = f"task must be one of {sorted(ENS_KINDS)} (got {task!r})"
+        raise ValueError(msg)
+    s = np.asarray(sums, dtype=np.float64).reshape(-1, SCORE_SUMS)
+    loss = _ratio(s[:, 0], s[:, 1])
+    n_nan, n_skipped = s[:, 2].astype(np.int64), s[:, 3].astype(np.int64)
+    if task == "regress":
+        if confusion is not None:
+            msg = "a confusion matrix goes with task='classif'"
+            raise ValueError(msg)
+        n = s[:, 1]
+        with np.errstate(all="ignore"):
+            rmse = np.sqrt(_ratio(s[:, 4], n))
+            pearson = _ratio(n * s[:, 10] - s[:, 6] * s[:, 7], np.sqrt((n * s[:, 8] - s[:, 6] ** 2) * (n * s[:, 9] - s[:, 7] ** 2)))
+            r2 = 1.0 - _ratio(s[:, 4], s[:, 9] - _ratio(s[:, 7] ** 2, n))
+        return Scores(loss, n.astype(np.int64), n_nan, n_skipped, rmse=rmse, mae=_ratio(s[:, 5], n), pearson=pearson, r2=r2)
+    n = s[:, 5]
+    res = Scores(loss, n.astype(np.int64), n_nan, n_skipped, accuracy=_ratio(s[:, 4], n))
+    if confusion is not None:
+        m = np.asarray(confusion, dtype=np.int64)
+        m = m.reshape(s.shape[0], m.shape[-2], m.shape[-1])
+        res.confusion = m
+        if m.shape[-1] == 2:
+            tn, fp, fn, tp = (m[:, i, j].astype(np.float64) for i, j in ((0, 0), (0, 1), (1, 0), (1, 1)))
+            res.tpr, res.tnr, res.precision = _ratio(tp, tp + fn), _ratio(tn, tn + fp), _ratio(tp, tp + fp)
+            with np.errstate(all="ignore"):
+                res.mcc = _ratio(tp * tn - fp * fn, np.sqrt((tp + fp) * (tp + fn) * (tn + fp) * (tn + fn)))
+    return res
+
+
+class MemberStopping:
+    """The early-stopping bookkeeping of ``train_ensemble``, host only: member
+    k's epoch improves when its validation loss falls below its best so far by
+    more than ``min_delta`` (the first finite loss always does; a NaN never
+    does); after ``patience`` epochs in a row without improvement the member is
+    stopped (``patience = None``: never).  ``best_epoch`` / ``stopped_epoch``:
+    int arrays [K], -1 for never."""
+
+    def __init__(self, k, patience=None, min_delta=0.0):
+        if patience is not None and int(patience) < 1:
+            msg = f"patience must be at least 1 (got {patience})"
+            raise ValueError(msg)
+        if not min_delta >= 0.0:
+            msg = f"min_delta must be >= 0 (got {min_delta})"
+            raise ValueError(msg)
+        self.patience = None if patience is None else int(patience)
+        self.min_delta = float(min_delta)
+        self.best = np.full(k, np.inf)
+        self.best_epoch = np.full(k, -1, dtype=np.int64)
+        self.stopped_epoch = np.full(k, -1, dtype=np.int64)
+        self.stalled = np.zeros(k, dtype=np.int64)
+
+    @property
+    def active(self):
+        """[K] bool: the members still training."""
+        return self.stopped_epoch < 0
+
+    def update(self, epoch, losses):
+        """Enter the epoch's validation losses [K] (a stopped member's entry is
+        ignored); returns the members whose best epoch this is."""
+        improved = []
+        for m, v in enumerate(np.asarray(losses, dtype=np.float64)):
+            if self.stopped_epoch[m] >= 0:
+                continue
+            if v < self.best[m] - self.min_delta:  # (False for NaN)
+                self.best[m], self.best_epoch[m], self.stalled[m] = v, epoch, 0
+                improved.append(m)
+                continue
+            self.stalled[m] += 1
+            if self.patience is not None and self.stalled[m] >= self.patience:
+                self.stopped_epoch[m] = epoch
+        return improved
+
+
 # Whether FusedEnsembleForward runs the multi-member launches by default (the
 # measurement behind the choice: DESIGN §5, profiles/ensemble_forward/)
 FUSED_FORWARD_DEFAULT = True
@@ -410,8 +669,10 @@ class FusedEnsembleForward:
     so in-place updates (a training step between two runs) are seen.
     """
 
-    def __init__(self, models, store, sizes, *, fused=None, captured=True):
+    def __init__(self, models, store, sizes, *, fused=None, captured=True, score=None):
         models = _check_members(models, "an ensemble forward")
+        if score is not None:
+            score = score.checked(models[0].output_shape)
         k = len(models)
         sizes = [[int(b) for b in s] for s in sizes]
         if len(sizes) != k:
@@ -449,6 +710,10 @@ class FusedEnsembleForward:
         self.handles, self.offs, self.n, self._probe = st.handles, st.offs, st.n, st.probe  # (the probe: the store's largest graph, for LDS and Z)
         with torch.cuda.device(dev):
             self.out = torch.zeros(k, st.n_max, self.out_dim, dtype=torch.float32, device=dev)
+        self.score = score
+        if score is not None:  # (score = None: no buffer, no launch)
+            self._score_launch = _ScoreLaunch(self.out, store.y, st.gids, self.n, score, probs=False)
+            self.sums, self.confusion = self._score_launch.sums, self._score_launch.confusion
         self._w = [self.spec.weights(ps) for ps in self.params]
         fwd = _lib.DR_PASS_FORWARD
         self._passes = [[make_pass(self.out_dim, fwd, out=self.out[m, o : o + b]) for o, b in zip(self.offs[m][:-1], sizes[m])] for m in range(k)]
@@ -486,6 +751,8 @@ class FusedEnsembleForward:
         for arr in self._members:
             rc = lib.dr_ginet_multi_pass(store.cstruct(), arr, len(self.models), lds, _lib.ptr(z), store.agg_x_stride if z is not None else 0, stream)
             _lib.check(rc, "dr_ginet_multi_pass")
+        if self.score is not None:  # the members' sums over the buffer just filled: the run's last launch
+            self._score_launch()
 
     def _sequential(self, batches):
         """Each member's batches in turn, by the launches ``model(batch)`` makes
@@ -501,6 +768,9 @@ class FusedEnsembleForward:
                         self.out[m, o : o + h.B].copy_(self.spec.layers(self.models[m], layered.batch_tensors(h), False))
                     else:
                         launch(self.spec, h, self._w[m], self._passes[m][s])
+        if self.score is not None:  # the launch the fused path ends with, on the same buffers: the same bits
+            self.staged.load(batches)
+            self._score_launch()
 
     def run(self, batches):
         """Predict ``batches[k][s]`` (arrays of graph ids of the store, sizes as
@@ -508,6 +778,9 @@ class FusedEnsembleForward:
         buffer that the next ``run`` overwrites."""
         batches = _check_batches(self.sizes, batches, self.store.packed.n_graphs)
         with torch.cuda.device(self.device):
+            if self.score is not None and self._score_launch.y is not self.store.y:  # set_targets() since the last run
+                self._score_launch = _ScoreLaunch(self.out, self.store.y, self.staged.gids, self.n, self.score, probs=False, sums=self.sums, confusion=self.confusion)
+                self.graph = None
             if not (self.fused and self.eligible()):
                 self.last_path = "sequential"
                 self._sequential(batches)
@@ -596,6 +869,38 @@ def predict_ensemble(models, dataset, indices=None, batch_size=64, task=None):
     return EnsemblePrediction(runner.out[:, : idx.size].clone(), mean, spread, label, idx)
 
 
+def score_ensemble(models, dataset, indices=None, batch_size=64, loss="mse", loss_param=None, class_weights=None, task=None):
+    """Score an ensemble against the store's targets: ``(Scores of the K
+    members, Scores of the ensemble, EnsemblePrediction)``.
+
+    ``predict_ensemble`` (its kept runner, its statistics launch) predicts
+    ``indices``; then two ``dr_ensemble_score`` launches: the members'
+    predictions, and the ensemble's ``mean`` as one more member row (for a
+    classifier the mean probability, scored with ``probs``: the loss is
+    -log p_y).  ``loss`` and its settings as the training step takes them;
+    ``task`` defaults to "classif" for the cross entropy and "regress"
+    otherwise and must agree with the loss.  A classifier's scores carry the
+    confusion matrix."""
+    classif = loss == "ce"
+    if task is None:
+        task = "classif" if classif else "regress"
+    if task not in ENS_KINDS or (task == "classif") != classif:
+        msg = f"task {task!r} does not go with loss {loss!r}: 'classif' scores the cross entropy, 'regress' the other losses"
+        raise ValueError(msg)
+    models = _check_members(models, "an ensemble score")
+    store = _store_of(dataset, _device_of(models))
+    pred = predict_ensemble(models, store, indices, batch_size, task)
+    with torch.cuda.device(store.device):
+        gids = torch.from_numpy(pred.indices).to(store.device)
+    kw = {"gids": gids, "loss": loss, "loss_param": loss_param, "class_weights": class_weights, "confusion": classif}
+    m_sums, m_conf = ensemble_score(pred.members, store.y, **kw)
+    e_sums, e_conf = ensemble_score(pred.mean.unsqueeze(0), store.y, probs=classif, **kw)
+    both = torch.cat([m_sums, e_sums]).cpu().numpy()  # one copy for the K + 1 rows
+    conf = None if not classif else torch.cat([m_conf, e_conf]).cpu().numpy()
+    k = m_sums.shape[0]
+    return (scores_from_sums(both[:k], None if conf is None else conf[:k], task), scores_from_sums(both[k:], None if conf is None else conf[k:], task), pred)
+
+
 MAX_KEPT_RUNNERS = 4
 
 
@@ -635,12 +940,22 @@ class _HeldOut:
     loss ``_held_out_loss`` forms, from the same predictions: the fp32 torch
     loss of each batch's slice, times its length, summed in float64."""
 
-    def __init__(self, ens: FusedEnsembleStep, store, val_indices, batch_size, fused=None):
+    def __init__(self, ens: FusedEnsembleStep, store, val_indices, batch_size, fused=None, device_loss=False):
         self.steps = ens.steps
         self.batches = [epoch_batches(v, batch_size, False, 0, 0, 0) for v in val_indices]
-        self.runner = FusedEnsembleForward(ens.models, store, [[len(b) for b in bs] for bs in self.batches], fused=fused)
+        st = ens.steps[0]
+        self.spec = ScoreSpec(st.loss, st.loss_param, st.class_weights) if device_loss else None
+        self.runner = FusedEnsembleForward(ens.models, store, [[len(b) for b in bs] for bs in self.batches], fused=fused, score=self.spec)
+        if device_loss:
+            return
         y = np.asarray(store.packed.y)
         self.y = [[torch.from_numpy(y[b]).to(ens.device, torch.float32) for b in bs] for bs in self.batches]
+
+    def scores(self):
+        """The held-out sets' ``Scores``, formed on the device by the run's last
+        launch: one run, one copy of K rows of doubles."""
+        self.runner.run(self.batches)
+        return scores_from_sums(self.runner.sums.cpu().numpy(), None, self.spec.task)
 
     def losses(self):
         outs = self.runner.run(self.batches)
@@ -689,7 +1004,8 @@ def out_of_fold_predictions(models, dataset, val_indices, batch_size=64):
     return pred, member
 
 
-def train_ensemble(models, dataset, member_indices=None, nepoch=1, batch_size=32, shuffle=True, seed=0, val_indices=None, val_fused=None, **step_kw):
+def train_ensemble(models, dataset, member_indices=None, nepoch=1, batch_size=32, shuffle=True, seed=0, val_indices=None, val_fused=None,
+                   val_loss="host", patience=None, min_delta=0.0, restore_best=False, **step_kw):  # fmt: skip
     """Train the members together over one resident dataset.
 
     ``dataset``: a ``GraphStore``, a dataset with ``graph_store(device)``, or a
@@ -703,9 +1019,35 @@ def train_ensemble(models, dataset, member_indices=None, nepoch=1, batch_size=32
     ran), or with ``fused = False`` by each member's own loop.  ``step_kw`` goes to
     ``FusedEnsembleStep``.  Training member k alone with ``FusedTrainStep`` over
     the same batches gives the same parameters and losses, bit for bit.
+
+    ``val_loss``: "host" (the default) forms each member's held-out loss with
+    torch from its batches' slices, a float64 sum of fp32 per-batch means;
+    "device" has the forward runner end with one ``dr_ensemble_score`` launch,
+    so an epoch's validation is one graph replay and one copy of K rows of
+    doubles, the loss is the loss over the whole held-out set (sum w l / sum w
+    with class weights) whatever ``batch_size`` cut it into, and
+    ``EnsembleResult.val_scores`` keeps every epoch's ``Scores``.  The two
+    differ in rounding (and, with class weights, in the weighting).
+
+    ``patience`` (needs ``val_indices``): member k stops after ``patience``
+    epochs in a row without its validation loss falling by more than
+    ``min_delta`` (a NaN loss is no improvement, ``MemberStopping``).  A
+    stopped member gets no batches in later epochs, its state stays bit for bit
+    as it was, and its ``train_loss`` and ``val_loss`` rows read NaN from then
+    on.  ``restore_best``: each member's parameters at its best epoch are kept
+    on the device and copied back at the end (the optimizer state stays the
+    last epoch's).  ``EnsembleResult.best_epoch`` / ``stopped_epoch`` [K], -1
+    for never.
     """
     models = list(models)
     k = len(models)
+    if val_loss not in ("host", "device"):
+        msg = f"val_loss must be 'host' or 'device' (got {val_loss!r})"
+        raise ValueError(msg)
+    if val_indices is None and (patience is not None or restore_best or val_loss == "device"):
+        msg = "patience, restore_best and val_loss='device' work on the held-out loss: give val_indices"
+        raise ValueError(msg)
+    stopping = MemberStopping(k, patience, min_delta) if val_indices is not None else None
     step_kw.setdefault("max_batch", batch_size)
     ens = FusedEnsembleStep(models, **step_kw)
     store = _store_of(dataset, ens.device)
@@ -715,12 +1057,18 @@ def train_ensemble(models, dataset, member_indices=None, nepoch=1, batch_size=32
         msg = f"member_indices / val_indices need one entry per member ({k})"
         raise ValueError(msg)
     train_loss = np.full((nepoch, k), np.nan)
+    device_loss = val_loss == "device"
     val_loss = None if val_indices is None else np.full((nepoch, k), np.nan)
+    val_scores = [] if device_loss else None
     # the held-out graphs of all members through one forward runner, built once
     # (fused = False: the members' own eval-mode loops, one after another)
-    val = _HeldOut(ens, store, val_indices, batch_size, val_fused) if val_indices is not None and ens.fused else None
+    val = _HeldOut(ens, store, val_indices, batch_size, val_fused if ens.fused else False, device_loss) if val_indices is not None and (ens.fused or device_loss) else None
+    best = [None] * k  # restore_best: each member's parameters at its best epoch (device copies)
     for epoch in range(nepoch):
-        batches = [epoch_batches(member_indices[m], batch_size, shuffle, seed, m, epoch) for m in range(k)]
+        active = np.ones(k, dtype=bool) if stopping is None else stopping.active
+        if not active.any():
+            break
+        batches = [epoch_batches(member_indices[m], batch_size, shuffle, seed, m, epoch) if active[m] else [] for m in range(k)]
         loss_sum = torch.zeros(k, dtype=torch.float64, device=ens.device)
         count = np.zeros(k, dtype=np.int64)
         for s in range(max(len(b) for b in batches)):
@@ -734,10 +1082,27 @@ def train_ensemble(models, dataset, member_indices=None, nepoch=1, batch_size=32
         for m in range(k):
             if count[m]:
                 train_loss[epoch, m] = float(total[m]) / int(count[m])
-        if val is not None:
+        if device_loss:
+            val_scores.append(val.scores())
+            val_loss[epoch] = val_scores[-1].loss
+        elif val is not None:
             val_loss[epoch] = val.losses()
         elif val_indices is not None:
             for m in range(k):
                 val_loss[epoch, m] = _held_out_loss(ens.steps[m], store, val_indices[m], batch_size)
+        if stopping is not None:
+            val_loss[epoch, ~active] = np.nan
+            for m in stopping.update(epoch, val_loss[epoch]):
+                if restore_best:
+                    with torch.no_grad():
+                        best[m] = [p.detach().clone() for p in models[m].ordered_params()]
+    if restore_best:
+        with torch.no_grad():
+            for m in range(k):
+                if best[m] is not None and stopping.best_epoch[m] != epoch:
+                    for p, b in zip(models[m].ordered_params(), best[m]):
+                        p.copy_(b)
     val_path = None if val_indices is None else "sequential" if val is None else val.runner.last_path
-    return EnsembleResult(train_loss, val_loss, models, val_path)
+    if stopping is None:
+        return EnsembleResult(train_loss, val_loss, models, val_path, step=ens)
+    return EnsembleResult(train_loss, val_loss, models, val_path, val_scores, stopping.best_epoch, stopping.stopped_epoch, ens)

@@ -856,6 +856,57 @@ int dr_reduce_update_multi(const void* dev_args, int32_t n_members, int32_t n_bl
 int dr_ensemble_stats(const float* out, int64_t member_stride, int32_t n_members, int32_t n, int32_t out_dim,
                       int32_t kind, float* mean, float* spread, int32_t* label, void* stream);
 
+/* The members' losses and metric sums against the store's targets, in one
+ * launch (replaces what a user computes by hand with torch and sklearn after
+ * K x Trainer.test(); the reference forms the loss per batch only,
+ * trainer.py:760-762).  out as dr_ensemble_stats takes it; member k scores its
+ * first n[k] rows (n: a HOST array of n_members counts, copied by value into
+ * the kernel arguments, so a captured launch holds constants).  Row i of member
+ * k has the target y[gids[k * gid_stride + i]] (gid_stride 0: every member
+ * scores the same ids), or y[i] with gids == NULL; y holds n_graphs floats.
+ *
+ * The per-graph term is formed in fp32 by the code the training pass uses
+ * (DR_LOSS_MSE d * d; L1 / SmoothL1 / Huber dr_regress_loss; DR_LOSS_CE
+ * class_w[y] * (mx + logf(sum expf(o - mx)) - o[y]), class_w [out_dim] or
+ * NULL); regression reads column 0.  With DR_SCORE_PROBS in flags out holds
+ * probabilities (the mean of dr_ensemble_stats) and the CE term is -logf(p_y).
+ * Everything is accumulated in fp64 into sums [n_members, DR_SCORE_SUMS]
+ * (every slot is written, zeros where unused):
+ *   regression      0 sum term   1 rows scored   2 rows whose term is NaN (they
+ *                   stay in the sums: the loss reads NaN, as torch's does)
+ *                   3 rows left out   4 sum d^2   5 sum |d|   6 sum o   7 sum y
+ *                   8 sum o^2   9 sum y^2   10 sum o y   (d = o - y; the
+ *                   products formed in double from the fp32 values)
+ *   classification  0 sum w_y l   1 sum w_y   2 rows with a NaN logit (in the
+ *                   sums, never correct, not in the confusion matrix)
+ *                   3 rows left out   4 correct rows (the label: the lowest
+ *                   index attaining the maximum)   5 rows scored (the accuracy's
+ *                   denominator: slot 1 is a sum of weights)
+ * confusion (optional, classification only) [n_members, out_dim, out_dim]
+ * int64: row = target, column = predicted label; every entry is written.
+ * A row is left out (slot 3, nothing else) when its graph id lies outside
+ * 0 .. n_graphs-1 or, in classification, its target is not an integer in
+ * 0 .. out_dim-1; y, class_w and confusion are never indexed by such a value.
+ *
+ * One 256-thread workgroup per member; thread t adds rows t, t + 256, ... in
+ * ascending order into its own doubles, and the partials are combined by the
+ * tree v[t] += v[t + s], s = 128 .. 1: no floating-point atomics, the result
+ * is a pure function of the inputs.  A member with n[k] == 0 gets zeros.
+ *
+ * Checked before any HIP call, DR_E_ARG for: a NULL out, y, n or sums;
+ * n_members outside 1..DR_MAX_MEMBERS; out_dim outside 1..DR_MAX_OUT; a
+ * negative n[k], n_graphs or gid_stride; member_stride < max n[k] * out_dim
+ * when n_members > 1; DR_LOSS_NONE, an unknown loss_kind or a loss_param the
+ * graph passes refuse; DR_LOSS_CE with out_dim < 2; DR_SCORE_PROBS or a
+ * confusion pointer with a regression loss; an unknown flag.  No allocation,
+ * copy or sync: capturable.                                                  */
+#define DR_SCORE_SUMS 12
+#define DR_SCORE_PROBS 1
+int dr_ensemble_score(const float* out, int64_t member_stride, const int64_t* gids, int64_t gid_stride,
+                      const float* y, int64_t n_graphs, const int32_t* n, int32_t n_members, int32_t out_dim,
+                      int32_t loss_kind, float loss_param, const float* class_w, int32_t flags, double* sums,
+                      int64_t* confusion, void* stream);
+
 /* ---- generic layer kernels (arbitrary edge lists; GINetConvLayer API) ---- */
 
 /* Stable CSR of (row, col) pairs sorted by row: rowptr [n_rows+1], perm [E]

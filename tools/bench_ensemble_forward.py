@@ -10,7 +10,10 @@ configs[1]-shape synthetic graphs, B = 64.
     * ``parent``    the per-member loop ``_held_out_loss``: K x 4 eager
                     ``model(batch)`` calls, one 64-workgroup launch each;
     * ``eager``     the fused runner issuing its 4 launches (grids (64, K));
-    * ``captured``  the same launches replayed as one HIP graph (the default).
+    * ``captured``  the same launches replayed as one HIP graph (the default);
+    * ``device_loss``  captured, with ``val_loss="device"``: the graph ends with
+                    one ``dr_ensemble_score`` launch and the phase with one
+                    copy of K rows of doubles (no torch loss call).
 
 (b) ``predict_ensemble`` over 1 024 graphs for K = 1, 4, 8 (16 multi-member
     launches in one graph, the statistics launch, a copy of the predictions)
@@ -21,7 +24,8 @@ Wall-clock us per phase / per call, each ending with the device idle (``--reps``
 calls per timing).  The variants are interleaved in one process and each runs
 ``--runs`` times; the table gives the mean and the spread (max - min) over the
 runs.  The last lines state, per K, whether the captured runner beats the
-parent's path by more than five times that path's own spread.
+parent's path by more than five times that path's own spread, and whether the
+device loss beats the captured runner's host loss by five times that one's.
 """
 
 from __future__ import annotations
@@ -83,6 +87,7 @@ def main():
     ap.add_argument("--members", type=int, nargs="+", default=[1, 4, 8])
     ap.add_argument("--reps", type=int, default=20, help="calls per timing")
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--what", choices=["both", "validate", "predict"], default="both", help="table (a), table (b), or both")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     n_graphs = max(max(args.folds) * HELD_OUT, PREDICT)
@@ -97,12 +102,16 @@ def main():
             print(f"{what:>8} {k:>2} {name:>12} {mean:10.1f} {spread:10.1f}  {' '.join(f'{x:.1f}' for x in t)}")
 
     # (a) the validation phase of K folds
-    for k in args.folds:
+    for k in args.folds if args.what != "predict" else []:
         ens = FusedEnsembleStep(models(k, dev, True), max_batch=B)
         val_idx = [np.arange(m * HELD_OUT, (m + 1) * HELD_OUT) for m in range(k)]
         captured = ensemble._HeldOut(ens, store, val_idx, B, fused=True)  # noqa: SLF001
         eager = ensemble._HeldOut(ens, store, val_idx, B, fused=True)  # noqa: SLF001
         eager.runner.captured = False
+        device = ensemble._HeldOut(ens, store, val_idx, B, fused=True, device_loss=True)  # noqa: SLF001
+
+        def device_loss():
+            return device.scores().loss  # noqa: B023
 
         def parent():
             return [ensemble._held_out_loss(st, store, v, B) for st, v in zip(ens.steps, val_idx)]  # noqa: SLF001, B023
@@ -111,16 +120,20 @@ def main():
         for held in (captured, eager):
             assert held.losses().tolist() == ref and held.runner.last_path == "fused", "the runner's losses are the parent loop's"
         assert captured.runner.graph is not None and eager.runner.graph is None
-        times = interleaved({"parent": parent, "eager": eager.losses, "captured": captured.losses}, args.runs, args.reps)
+        np.testing.assert_allclose(device_loss(), ref, rtol=1e-5, err_msg="the device loss is the host's up to rounding")
+        assert device.runner.last_path == "fused" and device.runner.graph is not None
+        times = interleaved({"parent": parent, "eager": eager.losses, "captured": captured.losses, "device_loss": device_loss}, args.runs, args.reps)
         report("validate", k, times)
         p, c = times["parent"], times["captured"]
         margin = 5 * (max(p) - min(p))
         verdicts.append({"what": "validate", "K": k, "parent_us": round(float(np.mean(p)), 2), "captured_us": round(float(np.mean(c)), 2), "five_spreads_us": round(margin, 2), "captured_wins": bool(np.mean(p) - np.mean(c) > margin)})
+        d, margin = times["device_loss"], 5 * (max(c) - min(c))  # the yardstick: the captured runner with the host loss
+        verdicts.append({"what": "val_loss", "K": k, "parent_us": round(float(np.mean(c)), 2), "captured_us": round(float(np.mean(d)), 2), "five_spreads_us": round(margin, 2), "captured_wins": bool(np.mean(c) - np.mean(d) > margin)})
 
     # (b) predict_ensemble against K EvalRunners in turn
     idx = np.arange(PREDICT)
     batches = epoch_batches(idx, B, False, 0, 0, 0)
-    for k in args.members:
+    for k in args.members if args.what != "validate" else []:
         ms = models(k, dev, False)
         runners = [EvalRunner(m, store, [len(b) for b in batches]) for m in ms]
 
@@ -139,6 +152,9 @@ def main():
         verdicts.append({"what": "predict", "K": k, "parent_us": round(float(np.mean(p)), 2), "captured_us": round(float(np.mean(c)), 2), "five_spreads_us": round(margin, 2), "captured_wins": bool(np.mean(p) - np.mean(c) > margin)})
 
     for v in verdicts:
+        if v["what"] == "val_loss":
+            print(f"{v['what']:>8} K={v['K']}: captured, host loss {v['parent_us']:.1f} us, captured, device loss {v['captured_us']:.1f} us, 5 x the host loss's spread {v['five_spreads_us']:.1f} us -> {'device loss wins' if v['captured_wins'] else 'no win'}")
+            continue
         print(f"{v['what']:>8} K={v['K']}: parent {v['parent_us']:.1f} us, fused+captured {v['captured_us']:.1f} us, 5 x parent's spread {v['five_spreads_us']:.1f} us -> {'fused wins' if v['captured_wins'] else 'no win'}")
     print(json.dumps({"bench": "ensemble_forward", "B": B, "held_out_per_member": HELD_OUT, "predict_graphs": PREDICT, "reps": args.reps, "runs": args.runs, "rows": rows, "verdicts": verdicts}))
 
