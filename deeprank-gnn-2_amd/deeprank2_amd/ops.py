@@ -91,6 +91,8 @@ def linear_xwT(x, w):
     m, k = x.shape
     n = w.shape[0]
     y = torch.empty(m, n, dtype=torch.float32, device=x.device)
+    if y.numel() == 0:  # torch gives an empty tensor a null data_ptr, which the C entry rejects
+        return y
     _lib.check(_lib.load().dr_linear_xwT(x.data_ptr(), w.data_ptr(), m, k, n, y.data_ptr(), _lib.stream_ptr(x.device)), "dr_linear_xwT")
     return y
 
@@ -101,6 +103,8 @@ def linear_xw(dy, w):
     m, n = dy.shape
     k = w.shape[1]
     dx = torch.empty(m, k, dtype=torch.float32, device=dy.device)
+    if dx.numel() == 0:
+        return dx
     _lib.check(_lib.load().dr_linear_xw(dy.data_ptr(), w.data_ptr(), m, n, k, dx.data_ptr(), _lib.stream_ptr(dy.device)), "dr_linear_xw")
     return dx
 
@@ -112,6 +116,8 @@ def linear_dw(dy, x):
     k = x.shape[1]
     n_split = max(1, min(64, m // 256))
     dw = torch.empty(n, k, dtype=torch.float32, device=dy.device)
+    if dw.numel() == 0:
+        return dw
     scratch = torch.empty(n_split * n * k, dtype=torch.float32, device=dy.device)
     _lib.check(_lib.load().dr_linear_dw(dy.data_ptr(), x.data_ptr(), m, n, k, dw.data_ptr(), scratch.data_ptr(), n_split, _lib.stream_ptr(dy.device)), "dr_linear_dw")
     return dw
@@ -137,11 +143,17 @@ def edge_graph(edge_index, n, ea):
     return EdgeGraph(edge_index, n, ea)
 
 
+def _wc_ptr(we, f):
+    """Address of the edge-feature columns we[:, 2F:].  Not the slice's own
+    data_ptr: with Fe = 0 the slice is empty, torch gives it a null pointer
+    and the C entries reject that."""
+    return we.data_ptr() + 2 * f * we.stride(1) * we.element_size()
+
+
 def edge_mlp_scatter(g: EdgeGraph, a, b, we, be, f, fe):
     """S = sum over CSR rows of relu(A_i + B_j + We[:, 2F:] ea_e + be) (32 channels)."""
     s = torch.empty(g.n, 32, dtype=torch.float32, device=a.device)
-    wc = we[:, 2 * f:]
-    _lib.check(_lib.load().dr_edge_mlp_scatter(g.rowptr.data_ptr(), g.col.data_ptr(), g.n, a.data_ptr(), b.data_ptr(), g.ea.data_ptr(), fe, wc.data_ptr(), we.stride(0), be.data_ptr(), s.data_ptr(), _lib.stream_ptr(a.device)), "dr_edge_mlp_scatter")
+    _lib.check(_lib.load().dr_edge_mlp_scatter(g.rowptr.data_ptr(), g.col.data_ptr(), g.n, a.data_ptr(), b.data_ptr(), g.ea.data_ptr(), fe, _wc_ptr(we, f), we.stride(0), be.data_ptr(), s.data_ptr(), _lib.stream_ptr(a.device)), "dr_edge_mlp_scatter")
     return s
 
 
@@ -150,6 +162,5 @@ def edge_mlp_scatter_bwd(g: EdgeGraph, a, b, we, be, f, fe, ds):
     d = torch.empty(g.n, 32, dtype=torch.float32, device=dev)
     dp = torch.empty_like(d)
     eap = torch.empty(g.n * 32 * max(fe, 1), dtype=torch.float32, device=dev)
-    wc = we[:, 2 * f:]
-    _lib.check(_lib.load().dr_edge_mlp_scatter_bwd(g.rowptr.data_ptr(), g.col.data_ptr(), g.trowptr.data_ptr(), g.tcol.data_ptr(), g.teid.data_ptr(), g.n, a.data_ptr(), b.data_ptr(), g.ea.data_ptr(), fe, wc.data_ptr(), we.stride(0), be.data_ptr(), ds.data_ptr(), d.data_ptr(), dp.data_ptr(), eap.data_ptr(), _lib.stream_ptr(dev)), "dr_edge_mlp_scatter_bwd")
+    _lib.check(_lib.load().dr_edge_mlp_scatter_bwd(g.rowptr.data_ptr(), g.col.data_ptr(), g.trowptr.data_ptr(), g.tcol.data_ptr(), g.teid.data_ptr(), g.n, a.data_ptr(), b.data_ptr(), g.ea.data_ptr(), fe, _wc_ptr(we, f), we.stride(0), be.data_ptr(), ds.data_ptr(), d.data_ptr(), dp.data_ptr(), eap.data_ptr(), _lib.stream_ptr(dev)), "dr_edge_mlp_scatter_bwd")
     return d, dp, eap
