@@ -28,7 +28,10 @@
 // Z depends only on the store's x and CSR, so by default it is built once per
 // store (dr_aggregate_x) and the Z-input kernels (graph_body<..., ZIN>) DMA each
 // graph's block into LDS instead of staging x / col / rowptr and gathering; the
-// gather kernels stay as the fallback (no array yet, DR_GINET_AGGX=0).
+// gather kernels stay as the fallback (no array yet, DR_GINET_AGGX=0).  The
+// record kernels (graph_body<..., ZIN, REC>) go one step further: every input
+// region of a graph but y is laid out once per store as the carve holds it
+// (dr_graph_records), and one linear copy stages the graph.
 // Roofline: HBM-bound on the compulsory inputs (x, CSR, clusters) and the
 // per-graph partial writes — see DESIGN.md §Roofline.
 
@@ -105,6 +108,15 @@ __host__ __device__ __forceinline__ void take_pool1_head(C& c, LdsWalk& w, int K
   w.take(c.head, HEADW);
   w.take(c.dgp, NW * 64);
 }
+// A graph's record (dr_graph_records), which is the Z-input carves' input
+// regions as they lie in LDS: Z (rows of c.LDW words), the depth-0 cluster of
+// each node, the pooled graph and the depth-1 members.
+template <class C>
+__host__ __device__ __forceinline__ void take_record_regions(C& c, LdsWalk& w, int N, int K0, int P1, int K1, int alias) {
+  w.take(c.z, N * c.LDW);
+  w.take(c.cl0, N);
+  take_pooled_inputs(c, w, K0, P1, K1, alias);
+}
 // The sixteen regions from p1 to dgp, in the order carve() and tail_carve()
 // share (everything the tail works in but the conv2 / head weights).
 template <class C>
@@ -139,15 +151,22 @@ __host__ __device__ __forceinline__ Carve carve(int N, int E, int F, int K0, int
   LdsWalk w;
   w.take(c.w1, 32 * F);  // [W1; W1e] (conv1 / conv1_ext .fc.weight), rows of F
   take_head_weights(c, w, OUT);
-  if (zs <= 0) w.take(c.x, N * c.XS);
-  w.take(c.z, N * c.LDW);
-  if (zs <= 0) {
+  if (zs > 0) {
+    // every input region directly after z, in the order of the graph's record
+    // (dr_graph_records): one linear copy stages them all
+    take_record_regions(c, w, N, K0, P1, K1, alias);
+    w.take(c.key, 2 * K0 * 32);
+    take_pool0(c, w, K0);
+    take_pool1_head(c, w, K0, K1);
+  } else {
+    w.take(c.x, N * c.XS);
+    w.take(c.z, N * c.LDW);
     w.take(c.rp, N + 1);
     w.take(c.col, (E + 1) / 2);  // uint16 column ids
+    w.take(c.cl0, N);            // depth-0 cluster of each node
+    w.take(c.key, 2 * K0 * 32);  // depth-0 pooling keys (uint64)
+    take_tail_regions(c, w, K0, P1, K1, alias);
   }
-  w.take(c.cl0, N);             // depth-0 cluster of each node
-  w.take(c.key, 2 * K0 * 32);   // depth-0 pooling keys (uint64)
-  take_tail_regions(c, w, K0, P1, K1, alias);
   w.take(c.keep, 32);  // 128 dropout keep bytes
   c.total = w.o;
   return c;
@@ -175,12 +194,12 @@ __host__ __device__ __forceinline__ void acc_take_weights(Carve& c, LdsWalk& w, 
 __host__ __device__ __forceinline__ void acc_take_inputs(Carve& c, LdsWalk& w, int N, int E, int K0, int P1, int K1, int alias,
                                                 int zs) {
   if (zs > 0) {  // Z is an input: one copy per parity, the next graph's DMA'd under this graph's tail
-    w.take(c.z, N * c.LDW);
-  } else {
-    w.take(c.x, N * c.XS);
-    w.take(c.rp, N + 1);
-    w.take(c.col, (E + 1) / 2);
+    take_record_regions(c, w, N, K0, P1, K1, alias);
+    return;
   }
+  w.take(c.x, N * c.XS);
+  w.take(c.rp, N + 1);
+  w.take(c.col, (E + 1) / 2);
   w.take(c.cl0, N);
   take_pooled_inputs(c, w, K0, P1, K1, alias);
 }
@@ -224,6 +243,18 @@ __host__ __device__ __forceinline__ AccLayout acc_layout(int Nm, int Em, int F, 
   return L;
 }
 
+// A record on its own: section offsets from its first word, and its length
+__host__ __device__ __forceinline__ Carve rec_layout(int N, int K0, int P1, int K1, int alias, int zs) {
+  Carve c;
+  c.LDW = zs;
+  LdsWalk w;
+  take_record_regions(c, w, N, K0, P1, K1, alias);
+  c.total = w.o;
+  return c;
+}
+// the words of a carve's record regions (z .. the end of m1i, the last of them)
+__host__ __device__ __forceinline__ int rec_words(const Carve& c, int K0) { return c.m1i + r4(K0) - c.z; }
+
 struct GinetArgs {
   dr_graph_store s;
   dr_ginet_weights w;
@@ -234,7 +265,15 @@ struct GinetArgs {
   // store-wide Z = A·X of dr_aggregate_x, node i of the store at z + i * z_stride
   int32_t z_stride = 0;
   const float* z = nullptr;
+  // the record kernels (dr_ginet_graph_pass_rec / dr_ginet_acc_pass_rec): the
+  // buffer of dr_graph_records; descs then points at dr_graph_rec_desc
+  // records (the sizes where dr_graph_desc has them, rec0 in the place of node0)
+  const float* rec = nullptr;
 };
+static_assert(sizeof(dr_graph_rec_desc) == sizeof(dr_graph_desc) && offsetof(dr_graph_rec_desc, rec0) == offsetof(dr_graph_desc, node0) &&
+                  offsetof(dr_graph_rec_desc, n_nodes) == offsetof(dr_graph_desc, n_nodes) &&
+                  offsetof(dr_graph_rec_desc, gid) == offsetof(dr_graph_desc, gid),
+              "the record kernels read dr_graph_rec_desc through dr_graph_desc");
 
 // ---- the head's fc1.weight [128, 64] in the two register layouts ginet_head reads ----
 //   row layout:    thread t holds W[t >> 3][8 * (t & 7) .. + 7]   (wave w: rows 8w .. 8w + 7, whole)
@@ -790,8 +829,12 @@ struct AccCtx {
 // sZ in the place of x, the column ids and the row pointers, and the gather
 // and the zeroing of Z's K padding are compiled out (the array holds the same
 // bits the gather would write, zeros past F).  From the MFMA on, the same code.
-template <int KPT, bool ACC = false, bool PF = false, bool ZIN = false>
+// REC (with ZIN): the graph's record (dr_graph_records) is that Z block with
+// every other input region behind it as the carve lists them: one copy in
+// 16-byte lanes, spread over the sixteen waves, stages the whole graph.
+template <int KPT, bool ACC = false, bool PF = false, bool ZIN = false, bool REC = false>
 __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx& ac) {
+  static_assert(ZIN || !REC, "a record holds Z");
   extern __shared__ __attribute__((aligned(16))) float lds_raw[];
   float* lds = lds_raw + (ACC ? ac.acc_words : 0);
   const int tid = dr_tid<ACC>();
@@ -812,10 +855,14 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   // Fetch every kernel-argument field the staging needs, and the descriptor,
   // in one scalar round trip each (hipcc would otherwise load them lazily
   // with a wait before each DMA).
-  asm volatile("" ::"s"(s.x), "s"(s.col), "s"(s.rowptr), "s"(s.cl0), "s"(s.p1_rowptr), "s"(s.p1_col),
-               "s"(s.p1t_rowptr), "s"(s.p1t_col), "s"(s.m1_ptr), "s"(s.m1_idx), "s"(s.y), "s"(F), "s"(alias),
-               "s"(OUT), "s"(n0), "s"(ec0), "s"(k00), "s"(q0), "s"(k10), "s"(N), "s"(E), "s"(K0), "s"(P1), "s"(K1),
-               "s"(g));
+  if (REC)  // (n0: the record's first word)
+    asm volatile("" ::"s"(a.rec), "s"(s.y), "s"(F), "s"(alias), "s"(OUT), "s"(n0), "s"(N), "s"(E), "s"(K0), "s"(P1), "s"(K1), "s"(g));
+  else
+    asm volatile("" ::"s"(s.x), "s"(s.col), "s"(s.rowptr), "s"(s.cl0), "s"(s.p1_rowptr), "s"(s.p1_col),
+                 "s"(s.p1t_rowptr), "s"(s.p1t_col), "s"(s.m1_ptr), "s"(s.m1_idx), "s"(s.y), "s"(F), "s"(alias),
+                 "s"(OUT), "s"(n0), "s"(ec0), "s"(k00), "s"(q0), "s"(k10), "s"(N), "s"(E), "s"(K0), "s"(P1), "s"(K1),
+                 "s"(g));
+  STAMP(23);  // (descriptor and kernel arguments in)
   const int zs = ZIN ? a.z_stride : 0;
   const Carve c = PF ? carve_acc(N, E, F, K0, P1, K1, alias, OUT, ac.lay, ac.par, zs) : carve(N, E, F, K0, P1, K1, alias, OUT, zs);
   const int LDW = c.LDW, XS = c.XS;
@@ -879,6 +926,10 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   auto stage_inputs = [&](const dr_graph_desc& dd, const Carve& cc) {
     const int64_t dn0 = dd.node0, dk00 = dd.k0;
     const int dg = dd.gid, dN = dd.n_nodes, dK0 = dd.n_k0;
+    if (REC) {  // the whole record, as it lies in HBM (dd.node0: its first word)
+      dma_copy<NT, 16, DMA_ASM>(lds + cc.z, a.rec + dn0, rec_words(cc, dK0) / 4, tid);
+      return;
+    }
     if (ZIN) {  // the graph's Z block as it lies in HBM (16-byte lanes where the stride gives 16-byte rows)
       if ((LDW & 3) == 0) dma_copy<NT, 16, DMA_ASM>(lds + cc.z, a.z + dn0 * (int64_t)LDW, dN * LDW / 4, tid);
       else dma_copy<NT, 4, DMA_ASM>(lds + cc.z, a.z + dn0 * (int64_t)LDW, dN * LDW, tid);
@@ -897,7 +948,9 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
     dma_copy<NT, 4, DMA_ASM>(lds + cc.m1p, s.m1_ptr + dd.k1 + dg, dd.n_k1 + 1, tid, 8);
     dma_copy<NT, 4, DMA_ASM>(lds + cc.m1i, s.m1_idx + dk00, dK0, tid, 1);
   };
-  if (!PF) {  // (every copy from wave 0: starting waves spread over the copies measured slower)
+  if (!PF && REC) {
+    dma_copy<NT, 16>(sZ, a.rec + n0, rec_words(c, K0) / 4, tid);
+  } else if (!PF) {  // (every copy from wave 0: starting waves spread over the copies measured slower)
     if (ZIN) {
       if ((LDW & 3) == 0) dma_copy<NT, 16>(sZ, a.z + n0 * (int64_t)LDW, N * LDW / 4, tid);
       else dma_copy<NT, 4>(sZ, a.z + n0 * (int64_t)LDW, N * LDW, tid);
@@ -918,7 +971,9 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   } else if (ac.first || *ac.staged == 0u) {
     stage_inputs(d, c);
   }
+  STAMP(24);  // (wave 0: the graph's last copy issued)
   if (!PF || ac.first) w1_stage<IMG>(sW1, sImg, a.w, F, tid);  // (last: ahead of the graph's copies it was 0.3 us slower)
+  STAMP(25);  // (conv1's weights issued)
   // ZIN: the front half is too short to cover the head weights' latency (it
   // showed as a wait before W2's and fc2's LDS stores), so they are requested
   // here, beside the staging DMA, and arrive with it: 10.50 -> 10.25 us per
@@ -938,7 +993,9 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   }
   // loaded late: no early wait (ACC: read once per launch by the kernel)
   if (a.p.step_counter) drop_offset = ACC ? (uint64_t)ac.step : (uint64_t)a.p.step_counter[0];
+  STAMP(26);  // (head weights requested, zeroing stores issued)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  STAMP(27);  // (wave 0's copies and loads landed)
   // snapshot for dr_reduce_update, stored only now so that no wait for the
   // counter load sits between the descriptor and the graph DMA
   if (a.p.step_counter && b == 0 && tid == 0) a.p.step_counter[1] = (int64_t)drop_offset;
@@ -1137,12 +1194,12 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
   return drop_offset;
 }
 
-template <int KPT, bool ZIN = false>
+template <int KPT, bool ZIN = false, bool REC = false>
 __global__ void __launch_bounds__(NT) ginet_graph_kernel(GinetArgs a) {
 #ifdef DR_STAMPS  // cross-kernel timeline (s_memrealtime, 100 MHz chip clock): slots 30 / 31 = entry / exit
   if (threadIdx.x == 0 && a.p.stamps) a.p.stamps[(int64_t)blockIdx.x * 32 + 30] = __builtin_amdgcn_s_memrealtime();
 #endif
-  graph_body<KPT, false, false, ZIN>(a, AccCtx{});
+  graph_body<KPT, false, false, ZIN, REC>(a, AccCtx{});
 #ifdef DR_STAMPS
   if (threadIdx.x == 0 && a.p.stamps) a.p.stamps[(int64_t)blockIdx.x * 32 + 31] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1315,7 +1372,7 @@ __host__ __device__ inline int acc_words(int F, int OUT, bool fc1_in_lds) {
   return 32 * F + 1024 + acc_head_words(OUT) + (fc1_in_lds ? 128 * 64 : 0);
 }
 
-template <int KPT, bool PF, bool ZIN = false>
+template <int KPT, bool PF, bool ZIN = false, bool REC = false>
 __global__ void __launch_bounds__(NT) ginet_acc_kernel(GinetArgs a, const int32_t* plan, AccLayout lay) {
   extern __shared__ __attribute__((aligned(16))) float lds_raw[];
   const int F = a.s.n_feat, OUT = a.p.out_dim, tid = threadIdx.x;
@@ -1349,7 +1406,7 @@ __global__ void __launch_bounds__(NT) ginet_acc_kernel(GinetArgs a, const int32_
     typedef const __attribute__((address_space(4))) GinetArgs* KArgs;
     KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("; dr_kargs" : "+s"(ka));
-    graph_body<KPT, true, PF, ZIN>(*(const GinetArgs*)ka, ac);
+    graph_body<KPT, true, PF, ZIN, REC>(*(const GinetArgs*)ka, ac);
     __syncthreads();  // the graph carve is restaged by the next graph
   }
   // the workgroup's row, then its loss sum
@@ -2009,7 +2066,7 @@ static int dispatch_kpt_zin(int F, bool zin, Launch launch) {
 // dr_ginet_graph_pass (z = null) and dr_ginet_graph_pass_z
 static int graph_pass_launch(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
                              const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes, const float* z,
-                             int32_t z_stride, void* stream) {
+                             int32_t z_stride, void* stream, const float* rec = nullptr) {
   DR_CHECK(graph_pass_check(store, descs, n_batch, w, pass, lds_bytes));
   if (n_batch == 0) return DR_OK;
   if (!store->cl0) return DR_E_ARG;
@@ -2021,8 +2078,11 @@ static int graph_pass_launch(const dr_graph_store* store, const dr_graph_desc* d
   args.B = n_batch;
   args.z = z;
   args.z_stride = z_stride;
-  return dispatch_kpt_zin(store->n_feat, z != nullptr, [&](auto kpt, auto zin) {
-    const auto kernel = &ginet_graph_kernel<decltype(kpt)::value, decltype(zin)::value>;
+  args.rec = rec;
+  return dispatch_kpt_zin(store->n_feat, z != nullptr || rec != nullptr, [&](auto kpt, auto zin) {
+    constexpr int KPT = decltype(kpt)::value;
+    constexpr bool ZIN = decltype(zin)::value;
+    const auto kernel = ZIN && rec ? &ginet_graph_kernel<KPT, ZIN, ZIN> : &ginet_graph_kernel<KPT, ZIN>;
     DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(kernel)));
     hipLaunchKernelGGL(kernel, dim3(n_batch), dim3(NT), lds_bytes, (hipStream_t)stream, args);
     return (int)hipGetLastError();
@@ -2053,6 +2113,19 @@ extern "C" int dr_ginet_graph_pass_z(const dr_graph_store* store, const dr_graph
                                      int32_t z_stride, void* stream) {
   if (!z_args_ok(store, z, z_stride)) return DR_E_ARG;
   return graph_pass_launch(store, descs, n_batch, w, pass, lds_bytes, z, z_stride, stream);
+}
+
+// the records' buffer: 16-byte aligned, for a usable stride
+static bool rec_args_ok(const dr_graph_store* store, const void* rdescs, const float* rec, int32_t z_stride) {
+  return rdescs && rec && reinterpret_cast<uintptr_t>(rec) % 16 == 0 && z_args_ok(store, rec, z_stride);
+}
+
+extern "C" int dr_ginet_graph_pass_rec(const dr_graph_store* store, const dr_graph_rec_desc* rdescs, int32_t n_batch,
+                                       const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes,
+                                       const float* rec, int32_t z_stride, void* stream) {
+  if (!rec_args_ok(store, rdescs, rec, z_stride)) return DR_E_ARG;
+  return graph_pass_launch(store, reinterpret_cast<const dr_graph_desc*>(rdescs), n_batch, w, pass, lds_bytes, nullptr,
+                           z_stride, stream, rec);
 }
 
 extern "C" int64_t dr_ginet_input_grad_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t n_feat, int32_t k0,
@@ -2161,7 +2234,8 @@ extern "C" int64_t dr_ginet_acc_lds_bytes(const int32_t* max_sizes, int32_t n_fe
 static int acc_pass_launch(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
                            const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes, int32_t n_groups,
                            const int32_t* plan, const int32_t* max_sizes, const float* z, int32_t z_stride,
-                           int32_t lds_z_bytes, void* stream) {
+                           int32_t lds_z_bytes, void* stream, const dr_graph_rec_desc* rdescs = nullptr) {
+  // (rdescs: z is the buffer of dr_graph_records, the record kernels run where the Z kernels would)
   if (!store || !descs || !w || !pass || n_batch < 0 || n_groups < 1) return DR_E_ARG;
   DR_CHECK(dr_check_loss(pass));
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
@@ -2200,14 +2274,20 @@ static int acc_pass_launch(const dr_graph_store* store, const dr_graph_desc* des
   args.p = *pass;
   args.descs = descs;
   args.B = n_batch;
-  args.z = z;
+  const bool rec = z && rdescs;
+  args.z = rec ? nullptr : z;
   args.z_stride = z ? z_stride : 0;
+  if (rec) {
+    args.rec = z;
+    args.descs = reinterpret_cast<const dr_graph_desc*>(rdescs);
+  }
   return dispatch_kpt_zin(F, z != nullptr, [&](auto kpt, auto zin) {
     constexpr int KPT = decltype(kpt)::value;
     constexpr bool ZIN = decltype(zin)::value;
     const bool prefetch = ZIN ? pf_z : pf;
     const int64_t bytes = ZIN ? (pf_z ? lds_pf_z : lds_z) : (pf ? lds_pf : lds);
-    const auto kernel = prefetch ? &ginet_acc_kernel<KPT, true, ZIN> : &ginet_acc_kernel<KPT, false, ZIN>;
+    const auto kernel = ZIN && rec ? (prefetch ? &ginet_acc_kernel<KPT, true, ZIN, ZIN> : &ginet_acc_kernel<KPT, false, ZIN, ZIN>)
+                                   : (prefetch ? &ginet_acc_kernel<KPT, true, ZIN> : &ginet_acc_kernel<KPT, false, ZIN>);
     DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(kernel)));
     hipLaunchKernelGGL(kernel, dim3(n_groups), dim3(NT), (int)bytes, (hipStream_t)stream, args, plan, L);
     return (int)hipGetLastError();
@@ -2226,6 +2306,15 @@ extern "C" int dr_ginet_acc_pass_z(const dr_graph_store* store, const dr_graph_d
                                    int32_t z_stride, void* stream) {
   if (!z_args_ok(store, z, z_stride) || lds_z_bytes < 0) return DR_E_ARG;
   return acc_pass_launch(store, descs, n_batch, w, pass, lds_bytes, n_groups, plan, max_sizes, z, z_stride, lds_z_bytes, stream);
+}
+
+extern "C" int dr_ginet_acc_pass_rec(const dr_graph_store* store, const dr_graph_desc* descs, const dr_graph_rec_desc* rdescs,
+                                     int32_t n_batch, const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes,
+                                     int32_t lds_z_bytes, int32_t n_groups, const int32_t* plan, const int32_t* max_sizes,
+                                     const float* rec, int32_t z_stride, void* stream) {
+  if (!rec_args_ok(store, rdescs, rec, z_stride) || lds_z_bytes < 0) return DR_E_ARG;
+  return acc_pass_launch(store, descs, n_batch, w, pass, lds_bytes, n_groups, plan, max_sizes, rec, z_stride, lds_z_bytes, stream,
+                         rdescs);
 }
 
 // ---------------------------------------------------------------------------
@@ -2261,6 +2350,72 @@ extern "C" int dr_aggregate_x(const dr_graph_store* store, float* z, int32_t z_s
   if (n_graphs == 0) return DR_OK;
   hipLaunchKernelGGL(aggregate_x_kernel, dim3(n_graphs), dim3(256), 0, (hipStream_t)stream, *store, z, z_stride, g0);
   return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// One record per graph (dr_graph_records): rec_layout's regions, the Z block
+// by aggregate_x_kernel's sum chain (from +0, one fp32 add per edge in CSR
+// order: the same bits), the index regions copied from the store's arrays,
+// every region's padding zero.  One workgroup per graph; not on the hot path.
+// ---------------------------------------------------------------------------
+namespace {
+__global__ void __launch_bounds__(256) graph_records_kernel(dr_graph_store s, float* out, int32_t z_stride, const int64_t* rec_off,
+                                                            int32_t g0) {
+  const int g = g0 + blockIdx.x;
+  const int64_t n0 = s.node_off[g], k00 = s.k0_off[g], q0 = s.p1_off[g], k10 = s.k1_off[g];
+  const int N = (int)(s.node_off[g + 1] - n0), K0 = (int)(s.k0_off[g + 1] - k00), P1 = (int)(s.p1_off[g + 1] - q0),
+            K1 = (int)(s.k1_off[g + 1] - k10);
+  const Carve c = rec_layout(N, K0, P1, K1, s.transpose_aliased, z_stride);
+  float* r = out + rec_off[g];
+  int32_t* ri = reinterpret_cast<int32_t*>(r);
+  const int32_t* rp = s.rowptr + n0 + g;
+  const uint16_t* col = s.col + s.col_off[g];
+  const float* x = s.x + n0 * (int64_t)s.x_stride;
+  for (int p = threadIdx.x; p < c.cl0; p += blockDim.x) {  // (c.cl0: the Z block's padded length; c.z = 0)
+    const int i = p / z_stride, k = p - i * z_stride;
+    float acc = 0.f;
+    if (i < N && k < s.n_feat)
+      for (int e = rp[i]; e < rp[i + 1]; ++e) acc = acc + x[(int64_t)col[e] * s.x_stride + k];
+    r[p] = acc;
+  }
+  auto put = [&](int at, const int32_t* src, int n) {
+    for (int p = threadIdx.x; p < r4(n); p += blockDim.x) ri[at + p] = p < n ? src[p] : 0;
+  };
+  put(c.cl0, s.cl0 + n0, N);
+  put(c.p1rp, s.p1_rowptr + k00 + g, K0 + 1);
+  put(c.p1c, s.p1_col + q0, P1);
+  if (!s.transpose_aliased) {
+    put(c.p1trp, s.p1t_rowptr + k00 + g, K0 + 1);
+    put(c.p1tc, s.p1t_col + q0, P1);
+  }
+  put(c.m1p, s.m1_ptr + k10 + g, K1 + 1);
+  put(c.m1i, s.m1_idx + k00, K0);
+}
+}  // namespace
+
+extern "C" int64_t dr_graph_record_words(int32_t n_nodes, int32_t k0, int32_t p1_edges, int32_t k1, int32_t transpose_aliased,
+                                         int32_t z_stride) {
+  if (n_nodes < 0 || k0 < 0 || p1_edges < 0 || k1 < 0 || z_stride < 1) return -1;
+  return rec_layout(n_nodes, k0, p1_edges, k1, transpose_aliased, z_stride).total;
+}
+
+extern "C" int dr_graph_records(const dr_graph_store* store, float* out, int32_t z_stride, const int64_t* rec_off, int32_t g0,
+                                int32_t n_graphs, void* stream) {
+  if (!store || !out || !rec_off || g0 < 0 || n_graphs < 0) return DR_E_ARG;
+  if (z_stride < store->n_feat || g0 + (int64_t)n_graphs > store->n_graphs) return DR_E_ARG;
+  if (reinterpret_cast<uintptr_t>(out) % 16 != 0) return DR_E_ARG;
+  if (n_graphs == 0) return DR_OK;
+  if (!store->cl0) return DR_E_ARG;
+  hipLaunchKernelGGL(graph_records_kernel, dim3(n_graphs), dim3(256), 0, (hipStream_t)stream, *store, out, z_stride, rec_off, g0);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dr_debug_graph_record(const int32_t* q, int32_t* offs) {
+  if (!q || !offs) return DR_E_ARG;
+  const Carve c = rec_layout(q[0], q[1], q[2], q[3], q[4], q[5]);
+  const int v[9] = {c.z, c.cl0, c.p1rp, c.p1c, c.p1trp, c.p1tc, c.m1p, c.m1i, c.total};
+  for (int i = 0; i < 9; ++i) offs[i] = v[i];
+  return DR_OK;
 }
 
 extern "C" int64_t dr_ginet_large_conv_lds_bytes(int32_t n_nodes, int32_t n_feat, int32_t k0, int32_t halo_max,

@@ -264,6 +264,11 @@ SIGNATURES = [
     ("dr_ginet_graph_pass_z", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, VP, ctypes.c_int32, VP]),
     ("dr_ginet_acc_pass_z", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, VP, _c_i32, VP, ctypes.c_int32, VP]),
     ("dr_ginet_z_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 9),
+    ("dr_graph_record_words", ctypes.c_int64, [ctypes.c_int32] * 6),
+    ("dr_graph_records", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, VP, ctypes.c_int32, ctypes.c_int32, VP]),
+    ("dr_ginet_graph_pass_rec", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, VP, ctypes.c_int32, VP]),
+    ("dr_ginet_acc_pass_rec", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, VP, _c_i32, VP, ctypes.c_int32, VP]),
+    ("dr_debug_graph_record", ctypes.c_int, [_c_i32, _c_i32]),
     ("dr_ginet_input_grad_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.POINTER(InputGradC), VP, ctypes.c_int32, ctypes.c_int32, VP]),
     ("dr_ginet_input_grad_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 9),
     ("dr_ginet_multi_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), ctypes.POINTER(GinetMemberC), ctypes.c_int32, ctypes.c_int32, VP, ctypes.c_int32, VP]),

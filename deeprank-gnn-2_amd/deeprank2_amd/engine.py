@@ -35,7 +35,7 @@ import ctypes
 import torch
 
 from deeprank2_amd import _lib, layered
-from deeprank2_amd.fused import BatchHandle, _device_cus, agg_x_for, capture_after_warmup, launch, lds_for, param_table, slab_rows_for, z_lds_for
+from deeprank2_amd.fused import BatchHandle, _device_cus, agg_x_for, capture_after_warmup, launch, lds_for, param_table, records_for, slab_rows_for, z_lds_for
 from deeprank2_amd.neuralnets.gnn.ginet import acc_recipe
 
 
@@ -421,9 +421,12 @@ class FusedTrainStep:
             return 0
         p.slab = self._acc_slab.data_ptr()
         z = agg_x_for(self.spec, h)
+        rec = records_for(self.spec, h) if z is not None else None
         lds, stream = lds_for(self.spec, h, self.out_dim), _lib.stream_ptr(self.device)
         try:  # (no plan: workgroup w runs positions w, w + r, ... — the same order eager and captured)
-            if z is not None:
+            if rec is not None:
+                rc = _lib.load().dr_ginet_acc_pass_rec(h.store.cstruct(), h.descs.data_ptr(), h.rdescs.data_ptr(), h.B, self._w, p, lds, z_lds_for(h, self.out_dim), r, None, self._acc_max_sizes(h), rec.data_ptr(), h.store.agg_x_stride, stream)
+            elif z is not None:
                 rc = _lib.load().dr_ginet_acc_pass_z(h.store.cstruct(), h.descs.data_ptr(), h.B, self._w, p, lds, z_lds_for(h, self.out_dim), r, None, self._acc_max_sizes(h), z.data_ptr(), h.store.agg_x_stride, stream)
             else:
                 rc = _lib.load().dr_ginet_acc_pass(h.store.cstruct(), h.descs.data_ptr(), h.B, self._w, p, lds, r, None, self._acc_max_sizes(h), stream)

@@ -30,6 +30,7 @@ class BatchHandle:
         self.gids_host = np.ascontiguousarray(gids_host, dtype=np.int32)
         self.gids = torch.from_numpy(self.gids_host).to(store.device)
         self.descs = store.descriptors(self.gids_host)
+        self.rdescs = store.record_descriptors(self.gids_host)  # (dr_graph_rec_desc, for the record entries)
         self.B = int(self.gids_host.size)
         self.max_sizes = store.max_sizes(self.gids_host)
         nf = store.packed.nonfinite
@@ -47,6 +48,7 @@ class BatchHandle:
         h.gids_host = np.zeros(b, dtype=np.int32)  # placeholder
         h.gids = None
         h.descs = descs
+        h.rdescs = None  # (rewritten descriptors: the Z-input entries)
         h.B = int(b)
         h.max_sizes = max_sizes
         h.nonfinite = False
@@ -446,6 +448,16 @@ def agg_x_for(spec: FusedSpec, h: BatchHandle):
     return h.store.agg_x()
 
 
+def records_for(spec: FusedSpec, h: BatchHandle):
+    """The store's graph records (``GraphStore.graph_records``) when this
+    batch's pass can stage from them (asked where :func:`agg_x_for` gave Z,
+    which stays the multi-member and input-gradient kernels' input and the
+    fallback; the handle must carry record descriptors), else None."""
+    if spec.entry != "dr_ginet_graph_pass" or h.nonfinite or getattr(h, "rdescs", None) is None:
+        return None
+    return h.store.graph_records()
+
+
 def z_lds_for(h: BatchHandle, out_dim):
     """Dynamic LDS bytes of the Z-input kernels for the batch's largest graph."""
     alias, f, zs = int(h.store.packed.transpose_aliased), h.store.n_feat, h.store.agg_x_stride
@@ -474,6 +486,11 @@ def launch(spec: FusedSpec, h: BatchHandle, w, p, wpack=None):
     lds = lds_for(spec, h, p.out_dim)
     if lds <= LDS_MAX and not (h.force_large and spec.large is not None):
         z = agg_x_for(spec, h)
+        rec = records_for(spec, h) if z is not None else None
+        if rec is not None:  # (fallbacks, as under capture: no records -> Z; no Z -> the gather entry)
+            rc = _lib.load().dr_ginet_graph_pass_rec(h.store.cstruct(), h.rdescs.data_ptr(), h.B, w, p, z_lds_for(h, p.out_dim), rec.data_ptr(), h.store.agg_x_stride, _lib.stream_ptr(h.store.device))
+            _lib.check(rc, "dr_ginet_graph_pass_rec")
+            return
         if z is not None:  # (the path was chosen by the gather form's LDS above; the per-graph Z carve drops x, rowptr and col for 2 N words and is always smaller)
             rc = _lib.load().dr_ginet_graph_pass_z(h.store.cstruct(), h.descs.data_ptr(), h.B, w, p, z_lds_for(h, p.out_dim), z.data_ptr(), h.store.agg_x_stride, _lib.stream_ptr(h.store.device))
             _lib.check(rc, "dr_ginet_graph_pass_z")

@@ -295,6 +295,17 @@ def records_from_batch(batch) -> list[GraphRecord]:
 
 DESC_DTYPE = np.dtype([("node0", "<i8"), ("col0", "<i8"), ("k0", "<i8"), ("p1", "<i8"), ("k1", "<i8"), ("n_nodes", "<i4"), ("n_edges", "<i4"), ("n_k0", "<i4"), ("n_p1", "<i4"), ("n_k1", "<i4"), ("gid", "<i4")])
 assert DESC_DTYPE.itemsize == 64  # dr_graph_desc
+REC_DESC_DTYPE = np.dtype([("rec0", "<i8"), ("reserved", "<i8", (4,)), ("n_nodes", "<i4"), ("n_edges", "<i4"), ("n_k0", "<i4"), ("n_p1", "<i4"), ("n_k1", "<i4"), ("gid", "<i4")])
+assert REC_DESC_DTYPE.itemsize == 64  # dr_graph_rec_desc
+
+
+def record_words(n, k0, p1, k1, alias, zs):
+    """Mirror of dr_graph_record_words, vectorised over graphs: the Z block, cl0,
+    the pooled CSR (and its transpose unless aliased) and the depth-1 members,
+    every region rounded up to 16 bytes."""
+    r4 = lambda v: (np.asarray(v, dtype=np.int64) + 3) & ~3  # noqa: E731
+    pooled = r4(np.asarray(k0) + 1) + r4(p1)
+    return r4(np.asarray(n, dtype=np.int64) * zs) + r4(n) + pooled * (1 if alias else 2) + r4(np.asarray(k1) + 1) + r4(k0)
 
 
 class GraphStore:
@@ -387,6 +398,14 @@ class GraphStore:
         self._agg_x = None
         # False: GINet's passes gather in the kernel (DR_GINET_AGGX=0 in the environment, read here once)
         self.use_agg_x = os.environ.get("DR_GINET_AGGX", "1") != "0"
+        # One record per graph (graph_records): the Z-input kernels' inputs as
+        # they lie in LDS, built on first need under the rules of agg_x.  The
+        # offsets (words) follow from the sizes alone, so handles made before
+        # the buffer exists already carry them (record_descriptors).
+        self._records = None
+        self.use_records = os.environ.get("DR_GINET_REC", "1") != "0"  # (A/B switch: the Z-input entries)
+        n, _, k0, p1, k1 = self._sizes
+        self.rec_off_host = np.concatenate([[0], np.cumsum(record_words(n, k0, p1, k1, p.transpose_aliased, self.agg_x_stride))]).astype(np.int64)
 
     @property
     def n_graphs(self):
@@ -463,6 +482,45 @@ class GraphStore:
             _lib.check(rc, "dr_aggregate_x")
             torch.cuda.current_stream(self.device).synchronize()  # later passes may run on other streams
         return z
+
+    def graph_records(self):
+        """Every graph's record (``dr_graph_records``), one fp32 buffer with
+        graph g's at word ``rec_off_host[g]``: what ``dr_ginet_graph_pass_rec``
+        / ``dr_ginet_acc_pass_rec`` stage by one linear copy.  Built on first
+        need and kept, under the rules of :meth:`agg_x` (its Z block is summed
+        here the same way, not copied from it): x and the cluster structures
+        are not written after construction; None when switched off with
+        ``use_agg_x`` and when still missing while the stream is capturing.
+        A record is the graph's Z block plus about 1 KB per residue graph."""
+        import torch  # noqa: PLC0415
+
+        from deeprank2_amd import _lib  # noqa: PLC0415
+
+        if not (self.use_agg_x and self.use_records):
+            return None
+        if self._records is None:
+            if self.device.type != "cuda" or torch.cuda.is_current_stream_capturing():
+                return None
+            with torch.cuda.device(self.device):
+                buf = torch.empty(max(4, int(self.rec_off_host[-1])), dtype=torch.float32, device=self.device)
+                off = torch.from_numpy(self.rec_off_host).to(self.device)
+                rc = _lib.load().dr_graph_records(self.cstruct(), buf.data_ptr(), self.agg_x_stride, off.data_ptr(), 0, self.n_graphs, _lib.stream_ptr(self.device))
+                _lib.check(rc, "dr_graph_records")
+                torch.cuda.current_stream(self.device).synchronize()  # later passes may run on other streams
+            self._records = buf
+        return self._records
+
+    def record_descriptors(self, gids_host):
+        """dr_graph_rec_desc records (64 bytes each) for these graph ids, as a device uint8 tensor."""
+        import torch  # noqa: PLC0415
+
+        g = np.asarray(gids_host, dtype=np.int64)
+        d = np.zeros(g.size, dtype=REC_DESC_DTYPE)
+        d["rec0"] = self.rec_off_host[g]
+        n, e, k0, p1, k1 = self._sizes
+        d["n_nodes"], d["n_edges"], d["n_k0"], d["n_p1"], d["n_k1"] = n[g], e[g], k0[g], p1[g], k1[g]
+        d["gid"] = g
+        return torch.from_numpy(d.view(np.uint8)).to(self.device)
 
     def descriptors(self, gids_host):
         """dr_graph_desc records (64 bytes each) for these graph ids, as a device uint8 tensor."""

@@ -303,6 +303,54 @@ int64_t dr_ginet_z_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t n_feat, i
                              int32_t p1_edges, int32_t k1, int32_t transpose_aliased, int32_t out_dim,
                              int32_t z_stride);
 
+/* ---- one record per graph: the Z-input kernels' inputs as they lie in LDS ----
+ * Nothing a graph brings to dr_ginet_graph_pass_z changes from step to step
+ * but y, and its input regions are a few words to 800 bytes each, every one a
+ * copy of its own from a store-wide array.  A record is those regions as the
+ * Z-input carve lists them, directly after one another from the carve's z, in
+ * 4-byte words, each region padded to 16 bytes with zeros:
+ *   [ Z: N * z_stride | cl0: N | p1_rowptr: K0 + 1 | p1_col: P1 |
+ *     (p1t_rowptr: K0 + 1 | p1t_col: P1   unless transpose_aliased) |
+ *     m1_ptr: K1 + 1 | m1_idx: K0 ]
+ * (row pointers graph-local, as in the store; the Z block holds the bits of
+ * dr_aggregate_x).  dr_graph_record_words: a record's length, a multiple of
+ * 4.  dr_graph_records writes the records of graphs g0 .. g0 + n_graphs - 1:
+ * graph g's at out + rec_off[g] (rec_off: device, indexed by the store's
+ * graph id, in words, multiples of 4; out 16-byte aligned).  Valid as long as
+ * x and the store's index arrays are unchanged.  DR_E_ARG for a NULL pointer,
+ * a z_stride below F or a graph range outside the store.                     */
+int64_t dr_graph_record_words(int32_t n_nodes, int32_t k0, int32_t p1_edges, int32_t k1, int32_t transpose_aliased,
+                              int32_t z_stride);
+int dr_graph_records(const dr_graph_store* store, float* out, int32_t z_stride, const int64_t* rec_off, int32_t g0,
+                     int32_t n_graphs, void* stream);
+
+/* One mini-batch slot of the record entries (64 bytes, one scalar load, the
+ * sizes where dr_graph_desc has them).                                       */
+typedef struct dr_graph_rec_desc {
+  int64_t rec0;        /* the record's first word in the record buffer */
+  int64_t reserved[4];
+  int32_t n_nodes, n_edges, n_k0, n_p1, n_k1, gid;
+} dr_graph_rec_desc;
+
+/* dr_ginet_graph_pass_z / dr_ginet_acc_pass_z staging each graph by ONE linear
+ * copy in 16-byte lanes of its record (rec: the buffer dr_graph_records
+ * filled for this z_stride) instead of one copy per region.  Same results,
+ * bit for bit; same checks, lds_bytes / lds_z_bytes and fallbacks as the _z
+ * entries (the accumulating pass falls back to the gather kernels where
+ * neither Z layout fits).  The store is still read for y.                    */
+int dr_ginet_graph_pass_rec(const dr_graph_store* store, const dr_graph_rec_desc* rdescs, int32_t n_batch,
+                            const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes,
+                            const float* rec, int32_t z_stride, void* stream);
+/* descs: the batch's dr_graph_desc records, read only by the gather fallback */
+int dr_ginet_acc_pass_rec(const dr_graph_store* store, const dr_graph_desc* descs, const dr_graph_rec_desc* rdescs,
+                          int32_t n_batch, const dr_ginet_weights* w, const dr_pass* pass, int32_t lds_bytes,
+                          int32_t lds_z_bytes, int32_t n_groups, const int32_t* plan, const int32_t* max_sizes,
+                          const float* rec, int32_t z_stride, void* stream);
+/* offs[0..8]: the record's section offsets z, cl0, p1_rowptr, p1_col,
+ * p1t_rowptr, p1t_col, m1_ptr, m1_idx and its length (words; q = N, K0, P1,
+ * K1, transpose_aliased, z_stride)                                           */
+int dr_debug_graph_record(const int32_t* q, int32_t* offs);
+
 /* ---- GINet input gradients (per-node attribution) -------------------------
  * The gradient of a GINet output with respect to the node features x
  * (GINetConvLayer.forward ginet.py:40-60 under GINet.forward ginet.py:90-125):

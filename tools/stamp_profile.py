@@ -76,6 +76,11 @@ def main():
         if np.median(full[:, :, 22]) > 0:
             g = np.median(full[:, :, 20] - full[:, :, 1]), np.median(full[:, :, 21] - full[:, :, 20]), np.median(full[:, :, 22] - full[:, :, 21])
             print(f"  wave 0 tile 0: gather {g[0]:.0f}  MFMA {g[1]:.0f}  pool atomics {g[2]:.0f} cyc")
+        if np.median(full[:, :, 27]) > 0:  # wave 0 inside the staging (stamps 23-27, between stamps 0 and 1)
+            marks = [("descriptor in", 23), ("carve done (stamp 0)", 0), ("last graph copy issued", 24), ("conv1 weights issued", 25), ("head weights requested, zeroing issued", 26), ("vmcnt(0) returned", 27), ("barrier passed (stamp 1)", 1)]
+            print("  wave 0 inside the staging, cycles since the previous mark:")
+            for (name, i), (_, j) in zip(marks[1:], marks[:-1]):
+                print(f"    {name:40s} {np.median(full[:, :, i] - full[:, :, j]):8.0f}")
 
 
 PHASES_F = ["stage", "gather rowmean(X)", "gemm conv1", "pool0", "conv2 (pooled)", "pool1+mean", "head fwd", "loss", "head/pool1/conv2 bwd", "dW1"]
