@@ -587,9 +587,11 @@ __global__ void __launch_bounds__(HT) vb_head(VA a) {
      // then the groups in order.  The chunk-fused forward leaves its tiles'
      // sums in part_mean; otherwise they are summed here from X2.  (Groups, not
      // one running sum: a group's 8 loads are in flight together.)
-    constexpr int CR = DR_VANILLA_CHUNK, GS = 8, NG = HT / 32;  // NG groups of GS chunks per round
+    constexpr int CR = DR_VANILLA_CHUNK, GS = 8;
+    // one thread per column and group: 32 columns per group (F <= 32), 64 beyond
+    const int CS = F > 32 ? 6 : 5, NG = HT >> CS;  // NG groups of GS chunks per round
     const int nch = (N + CR - 1) / CR;
-    const int n = tid & 31, gq = tid >> 5;
+    const int n = tid & ((1 << CS) - 1), gq = tid >> CS;
     float t = 0.f;  // thread n < F: the ordered sum over the groups
     for (int g0 = 0; g0 * GS < nch; g0 += NG) {
       const int c0 = (g0 + gq) * GS;
@@ -627,7 +629,7 @@ __global__ void __launch_bounds__(HT) vb_head(VA a) {
       sRed[tid] = gs;
       __syncthreads();
       if (tid < F)
-        for (int q = 0; q < NG && (g0 + q) * GS < nch; ++q) t += sRed[q * 32 + tid];
+        for (int q = 0; q < NG && (g0 + q) * GS < nch; ++q) t += sRed[(q << CS) + tid];
       __syncthreads();
     }
     if (tid < F) sG[tid] = t / (float)N;

@@ -176,7 +176,10 @@ def make_spec(f, fe):
         lds = int(lib.dr_vanilla_lds_bytes(f, fe, p.out_dim))
         _lib.check(lib.dr_vanilla_graph_pass(st.cstruct(), h.descs.data_ptr(), h.B, w, p, sc, lds, _lib.stream_ptr(st.device)), "dr_vanilla_graph_pass")
 
-    return FusedSpec(PARAM_NAMES, recipe, slab_stride, head_stride, "dr_vanilla_graph_pass", weights, lambda *_: 0, dropout=0.0, run=run, slab_rows=MAX_SPLIT, slab_k=lambda h: split_k(h, f, fe), handoffs=True, wpack=packed)
+    # only the per-graph kernel reads the packed copy (dr_vanilla_wpack: F <= 32,
+    # Fe <= 4); wider models always run the pipeline and have none
+    wpack = packed if f <= 32 and fe <= FUSED_MAX_FE else None  # noqa: PLR2004
+    return FusedSpec(PARAM_NAMES, recipe, slab_stride, head_stride, "dr_vanilla_graph_pass", weights, lambda *_: 0, dropout=0.0, run=run, slab_rows=MAX_SPLIT, slab_k=lambda h: split_k(h, f, fe), handoffs=True, wpack=wpack)
 
 
 FUSED_MAX_FE = 4  # vanilla_graph.hip MAXFE

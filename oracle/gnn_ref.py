@@ -197,7 +197,7 @@ class VanillaConvolutionalLayer(nn.Module):
     def forward(self, node_features, edge_node_indices, edge_features):
         a, b = edge_node_indices
         m = self._edge_mlp(torch.cat([node_features[a], node_features[b], edge_features], dim=1))
-        acc = torch.zeros(node_features.shape[0], m.shape[1]).to(node_features.device)
+        acc = torch.zeros(node_features.shape[0], m.shape[1], dtype=m.dtype).to(node_features.device)
         s = P.scatter_sum(m, a, dim=0, out=acc)
         return self._node_mlp(torch.cat([node_features, s], dim=1))
 
