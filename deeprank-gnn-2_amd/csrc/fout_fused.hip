@@ -823,11 +823,16 @@ __global__ void __launch_bounds__(NT) fout_graph_kernel(FoutArgs a) {
           arg = i;
         }
       }
-      tb[p] = best;
-      ta[p] = arg;
+      if (LS == 0) {  // one slice per pair: nothing to combine, and K0 > 64 has more pairs than tb / ta hold (NT each)
+        sP1[p] = (best == LOWEST) ? 0.f : best;
+        sA1[p] = arg;
+      } else {
+        tb[p] = best;
+        ta[p] = arg;
+      }
     }
     __syncthreads();
-    for (int p = tid; p < pairs; p += NT) {
+    for (int p = tid; LS > 0 && p < pairs; p += NT) {
       float best = LOWEST;
       int arg = N;
       for (int sl = 0; sl < S1; ++sl) {

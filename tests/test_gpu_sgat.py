@@ -1,7 +1,8 @@
 """GPU parity of the MI355X SGAT path (dr_sgat_graph_pass + dr_reduce_update;
 dr_spmm_csr_w + linear kernels for SGraphAttentionLayer) against goldens
 generated from the reference's sgat.py and the CPU oracle.  Tolerance: 1e-4
-(north_star, fp32)."""
+(north_star, fp32).  Other node-feature widths and up to 16 outputs are in
+test_gpu_widths.py."""
 
 from __future__ import annotations
 
