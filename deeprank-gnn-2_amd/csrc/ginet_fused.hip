@@ -390,6 +390,42 @@ __device__ __forceinline__ void w1_operands(const float* sW1, const float* img, 
   do {            \
   } while (0)
 #endif
+// -DDR_STAMPS=2: marks inside three tail phases as well (stamps 15-19, 28).
+// Each waits for wave 0's LDS reads first, which ends the overlap the phase
+// has without it: read these apart from the phase table of -DDR_STAMPS.
+#if defined(DR_STAMPS) && DR_STAMPS >= 2
+// (SUBSTAMP: in a `for (p = tid; ...)` loop, the first item only)
+#define SUBSTAMP0(i)                                                                              \
+  do {                                                                                            \
+    __builtin_amdgcn_sched_barrier(0);                                                            \
+    if (tid < 64 && a.p.stamps) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                \
+    if (tid == 0 && a.p.stamps) a.p.stamps[(int64_t)b * 32 + (i)] = __builtin_amdgcn_s_memtime(); \
+    __builtin_amdgcn_sched_barrier(0);                                                            \
+  } while (0)
+#define SUBSTAMP(i)          \
+  do {                       \
+    if (p < NT) SUBSTAMP0(i); \
+  } while (0)
+#else
+#define SUBSTAMP0(i) \
+  do {               \
+  } while (0)
+#define SUBSTAMP(i) \
+  do {              \
+  } while (0)
+#endif
+
+// f(integral_constant<int, M>) with M = min(n, G) for a wave-uniform n >= 1
+// (n <= 0: nothing): a group of exactly M items, every slot of it live
+template <int G, class F>
+__device__ __forceinline__ void uniform_group(int n, F&& f) {
+  if constexpr (G > 1) {
+    if (n >= G) f(std::integral_constant<int, G>());
+    else uniform_group<G - 1>(n, f);
+  } else {
+    if (n >= 1) f(std::integral_constant<int, 1>());
+  }
+}
 
 // sum over a pooled CSR row [eb, ee) of v[col[e] * 64 + o], in edge order;
 // four index reads, then four value reads in flight per step (same sum order
@@ -483,19 +519,47 @@ __device__ __forceinline__ void ginet_tail(const GinetArgs& a, const TailLds& t,
       wr[4 * q + 3] = v.w;
     }
     float acc = 0.f;
-    for (int e = t.p1rp[k]; e < t.p1rp[k + 1]; ++e) {
-      float y = 0.f;
-      const float* pr = t.p1 + t.p1c[e] * 32 + br * 16;
+    SUBSTAMP(15);
+    // the row's neighbours two at a time and a last one alone: the group's
+    // column ids, then its half-rows of P1 in flight, one chain per neighbour,
+    // and the sums added in edge order.  (Groups of four hold 64 row values:
+    // 113-127 VGPRs and scratch in three accumulating kernels.)
+    // (k = p >> 6 is the same for a wave's 64 lanes: the row's bounds in
+    // SGPRs, the group size a scalar branch.  A group never has an idle slot:
+    // these phases are bound by the instructions one wave issues, and a
+    // predicated group of fixed width ran its idle slots' instructions too)
+    constexpr int G2 = 2;
+    const int eb = __builtin_amdgcn_readfirstlane(t.p1rp[k]), ee = __builtin_amdgcn_readfirstlane(t.p1rp[k + 1]);
+    for (int e0 = eb; e0 < ee; e0 += G2) {
+      uniform_group<G2>(ee - e0, [&](auto m_t) {
+        constexpr int M = decltype(m_t)::value;
+        int c[M];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 v = *reinterpret_cast<const float4*>(pr + 4 * q);
-        y = fmaf(v.x, wr[4 * q], y);
-        y = fmaf(v.y, wr[4 * q + 1], y);
-        y = fmaf(v.z, wr[4 * q + 2], y);
-        y = fmaf(v.w, wr[4 * q + 3], y);
-      }
-      acc += y;
+        for (int u = 0; u < M; ++u) c[u] = t.p1c[e0 + u];
+        float4 v[M][4];
+#pragma unroll
+        for (int u = 0; u < M; ++u) {
+          const float* pr = t.p1 + c[u] * 32 + br * 16;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) v[u][q] = *reinterpret_cast<const float4*>(pr + 4 * q);
+        }
+        float y[M];
+#pragma unroll
+        for (int u = 0; u < M; ++u) {
+          y[u] = 0.f;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            y[u] = fmaf(v[u][q].x, wr[4 * q], y[u]);
+            y[u] = fmaf(v[u][q].y, wr[4 * q + 1], y[u]);
+            y[u] = fmaf(v[u][q].z, wr[4 * q + 2], y[u]);
+            y[u] = fmaf(v[u][q].w, wr[4 * q + 3], y[u]);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < M; ++u) acc += y[u];
+      });
     }
+    SUBSTAMP(16);
     const float h2v = relu_keepnan(acc);
     t.h2[p] = h2v;
     if (one_cl) __hip_atomic_fetch_max(reinterpret_cast<uint32_t*>(t.p2) + o, __float_as_uint(h2v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -635,21 +699,64 @@ __device__ __forceinline__ void ginet_tail(const GinetArgs& a, const TailLds& t,
     for (int rc = 0; rc < NW; ++rc) dgs += t.dgp[rc * 64 + o];
     const float dgo = dgs / (float)K1;
     float acc = 0.f;
+    // every loop below goes four items at a time and the rest (1-3) as a
+    // group of exactly that size, a group's reads in flight together (index
+    // reads, then the gathers); the sums keep their terms and their order.
+    // (j = p >> 6 is wave-uniform: the transposed row's bounds in SGPRs)
+    const int eb = __builtin_amdgcn_readfirstlane(t.p1trp[j]), ee = __builtin_amdgcn_readfirstlane(t.p1trp[j + 1]);
+    SUBSTAMP(17);
     if (one_cl) {  // the one cluster's tie count per channel, here instead of in the pooling step
       const float mx = t.p2[o];
       float ties = 0.f;
-      for (int q = 0; q < K0; ++q) ties += (t.h2[q * 64 + o] == mx) ? 1.f : 0.f;
-      for (int e = t.p1trp[j]; e < t.p1trp[j + 1]; ++e) {
-        const float h = t.h2[t.p1tc[e] * 64 + o];
-        acc += relu_bwd(h, (h == mx ? 1.f : 0.f) * (dgo / ties));
+      for (int q0 = 0; q0 < K0; q0 += 4) {
+        uniform_group<4>(K0 - q0, [&](auto m_t) {
+          constexpr int M = decltype(m_t)::value;
+          float hv[M];
+#pragma unroll
+          for (int u = 0; u < M; ++u) hv[u] = t.h2[(q0 + u) * 64 + o];
+#pragma unroll
+          for (int u = 0; u < M; ++u) ties += (hv[u] == mx) ? 1.f : 0.f;
+        });
+      }
+      SUBSTAMP(18);
+      for (int e0 = eb; e0 < ee; e0 += 4) {
+        uniform_group<4>(ee - e0, [&](auto m_t) {
+          constexpr int M = decltype(m_t)::value;
+          int c[M];
+#pragma unroll
+          for (int u = 0; u < M; ++u) c[u] = t.p1tc[e0 + u];
+          float h[M];
+#pragma unroll
+          for (int u = 0; u < M; ++u) h[u] = t.h2[c[u] * 64 + o];
+#pragma unroll
+          for (int u = 0; u < M; ++u) acc += relu_bwd(h[u], (h[u] == mx ? 1.f : 0.f) * (dgo / ties));
+        });
       }
     } else {
-      for (int e = t.p1trp[j]; e < t.p1trp[j + 1]; ++e) {
-        const int k = t.p1tc[e], mo = t.cl1[k] * 64 + o;
-        const float h = t.h2[k * 64 + o];
-        acc += relu_bwd(h, (h == t.p2[mo] ? 1.f : 0.f) * (dgo / t.nt[mo]));
+      SUBSTAMP(18);
+      for (int e0 = eb; e0 < ee; e0 += 4) {
+        uniform_group<4>(ee - e0, [&](auto m_t) {
+          constexpr int M = decltype(m_t)::value;
+          int c[M], mo[M];
+#pragma unroll
+          for (int u = 0; u < M; ++u) c[u] = t.p1tc[e0 + u];
+          float h[M], pm[M], tn[M];
+#pragma unroll
+          for (int u = 0; u < M; ++u) {
+            mo[u] = t.cl1[c[u]] * 64 + o;
+            h[u] = t.h2[c[u] * 64 + o];
+          }
+#pragma unroll
+          for (int u = 0; u < M; ++u) {
+            pm[u] = t.p2[mo[u]];
+            tn[u] = t.nt[mo[u]];
+          }
+#pragma unroll
+          for (int u = 0; u < M; ++u) acc += relu_bwd(h[u], (h[u] == pm[u] ? 1.f : 0.f) * (dgo / tn[u]));
+        });
       }
     }
+    SUBSTAMP(19);
     t.y2[p] = acc;
   }
   __syncthreads();
@@ -679,12 +786,26 @@ __device__ __forceinline__ void ginet_tail(const GinetArgs& a, const TailLds& t,
       if (ACC) t.acc[32 * F + p] += acc;
       else drk::st_part(slab + p, acc);
     }
+    SUBSTAMP0(28);
     for (int p = tid; p < K0 * 32; p += NT) {
       const int k = p >> 5, ch = p & 31, br = ch >> 4, j = ch & 15;
       const float* wb = t.w2 + br * 512;
       float acc = 0.f;
-#pragma unroll 8
-      for (int o = 0; o < 32; ++o) acc = fmaf(t.y2[k * 64 + br * 32 + o], wb[o * 16 + j], acc);
+      // the 32 + 32 operands in flight at once (dY2's half-row as eight
+      // 16-byte reads), then the same chain
+      float4 yv[8];
+      float wv[32];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) yv[q] = *reinterpret_cast<const float4*>(t.y2 + k * 64 + br * 32 + 4 * q);
+#pragma unroll
+      for (int o = 0; o < 32; ++o) wv[o] = wb[o * 16 + j];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        acc = fmaf(yv[q].x, wv[4 * q], acc);
+        acc = fmaf(yv[q].y, wv[4 * q + 1], acc);
+        acc = fmaf(yv[q].z, wv[4 * q + 2], acc);
+        acc = fmaf(yv[q].w, wv[4 * q + 3], acc);
+      }
       const int i = t.a1[p];
       t.dp1[p] = (i < N) ? relu_bwd(t.p1[p], acc) : 0.f;  // P1 = H1[arg] exactly
     }

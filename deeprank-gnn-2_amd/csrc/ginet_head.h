@@ -49,6 +49,14 @@ __device__ __forceinline__ void head_stamp(int64_t* row, int i) {
 #endif
 }
 
+// eight consecutive LDS words as two 16-byte reads (src 16-byte aligned: the
+// head's vectors start their regions or lie a multiple of 64 words in)
+__device__ __forceinline__ void ld8(float (&v)[8], const float* src) {
+  const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
 // a per-graph partial's store
 __device__ __forceinline__ void st_part(float* p, float v) { *p = v; }
 
@@ -68,8 +76,10 @@ __device__ __forceinline__ bool ginet_head(const dr_pass& p, const GinetHeadLds&
   {
     const int r = tid >> 3, part = tid & 7;  // 8 lanes per fc1 row
     float acc = 0.f;
+    float gj[8];
+    ld8(gj, t.g + part * 8);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc = fmaf(t.g[part * 8 + j], fc1_row[j], acc);
+    for (int j = 0; j < 8; ++j) acc = fmaf(gj[j], fc1_row[j], acc);
     acc = dr_sum8(acc);  // the xor-1,2,4 butterfly sums, on the DPP path
     if (part == 0) {
       acc += fc1_bias;
@@ -165,8 +175,10 @@ __device__ __forceinline__ bool ginet_head(const dr_pass& p, const GinetHeadLds&
   {
     const int o = tid & 63, rc = dr_wave<ACC>(tid);  // 16 chunks of 8 fc1 rows
     float acc = 0.f;
+    float dj[8];
+    ld8(dj, t.dh + rc * 8);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc = fmaf(fc1_col[j], t.dh[rc * 8 + j], acc);
+    for (int j = 0; j < 8; ++j) acc = fmaf(fc1_col[j], dj[j], acc);
     t.dgp[rc * 64 + o] = acc;
   }
   __syncthreads();

@@ -6,6 +6,11 @@ ginet_nocluster_kernel) from the stamps build.
 Stamps (s_memtime, shader clock cycles) are taken by thread 0 right after each
 phase barrier; the build that takes them is never used for timing claims —
 read the shares, not the absolute length.
+
+A library built with -DDR_STAMPS=2 (tools/build_variant.sh) also marks wave 0
+inside gemm2+spmm2, pool1-bwd and dW2+dP1, printed below the phase table.  Each
+of those marks waits for the wave's LDS reads first, so it ends the overlap
+the phase has without it: take the phase table from a -DDR_STAMPS build.
 """
 
 from __future__ import annotations
@@ -76,6 +81,16 @@ def main():
         if np.median(full[:, :, 22]) > 0:
             g = np.median(full[:, :, 20] - full[:, :, 1]), np.median(full[:, :, 21] - full[:, :, 20]), np.median(full[:, :, 22] - full[:, :, 21])
             print(f"  wave 0 tile 0: gather {g[0]:.0f}  MFMA {g[1]:.0f}  pool atomics {g[2]:.0f} cyc")
+        if np.median(full[:, :, 19]) > 0:  # wave 0 inside three tail phases (stamps 15-19, 28; its LDS reads waited for at each)
+            subs = [
+                ("gemm2+spmm2", [(4, "phase start"), (15, "W2 rows read"), (16, "edge loop done"), (5, "H2 stored, barrier passed")]),
+                ("pool1-bwd", [(10, "phase start"), (17, "dgp, p2 (and H2 column) read"), (18, "ties counted"), (19, "edge loop done"), (11, "dY2 stored, barrier passed")]),
+                ("dW2+dP1", [(12, "phase start"), (28, "dW2 item done"), (13, "dP1 item done, barrier passed")]),
+            ]
+            for title, marks in subs:
+                print(f"  wave 0 inside {title}, cycles since the previous mark:")
+                for (i, name), (j, _) in zip(marks[1:], marks[:-1]):
+                    print(f"    {name:40s} {np.median(full[:, :, i] - full[:, :, j]):8.0f}")
         if np.median(full[:, :, 27]) > 0:  # wave 0 inside the staging (stamps 23-27, between stamps 0 and 1)
             marks = [("descriptor in", 23), ("carve done (stamp 0)", 0), ("last graph copy issued", 24), ("conv1 weights issued", 25), ("head weights requested, zeroing issued", 26), ("vmcnt(0) returned", 27), ("barrier passed (stamp 1)", 1)]
             print("  wave 0 inside the staging, cycles since the previous mark:")
