@@ -940,6 +940,11 @@ struct AccCtx {
   // PF: LDS word set to 1 by the graph whose idle waves staged the next
   // graph's inputs (read by that next graph before its staging)
   uint32_t* staged = nullptr;
+  // graph_body<..., IG = true> (ginet_integrated_grad_kernel): the step's
+  // point alpha of the path from the baseline, and the baseline's store-wide
+  // Zb = A xb in the layout of a.z (null: a zero baseline)
+  float ig_alpha = 1.f;
+  const float* ig_zb = nullptr;
 };
 
 // KPT: conv1's K (F) padded to whole 16-deep MFMA steps, 32 (F <= 32) or 64.
@@ -953,14 +958,20 @@ struct AccCtx {
 // REC (with ZIN): the graph's record (dr_graph_records) is that Z block with
 // every other input region behind it as the carve lists them: one copy in
 // 16-byte lanes, spread over the sixteen waves, stages the whole graph.
-template <int KPT, bool ACC = false, bool PF = false, bool ZIN = false, bool REC = false>
+// IG (with ZIN, 16-byte Z rows): the pass runs at the point ac.ig_alpha of the
+// straight path from a baseline to x.  Z is linear in x, so each wave rescales
+// the staged rows of its own tile in place before its MFMA reads them, to
+// alpha * Z (zero baseline) or Zb + alpha * (Z - Zb); the tail then sees that Z.
+template <int KPT, bool ACC = false, bool PF = false, bool ZIN = false, bool REC = false, bool IG = false>
 __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx& ac) {
   static_assert(ZIN || !REC, "a record holds Z");
+  static_assert(!IG || (ZIN && !REC && !ACC && !PF), "the path's points are formed on the per-graph Z-input form");
   extern __shared__ __attribute__((aligned(16))) float lds_raw[];
   float* lds = lds_raw + (ACC ? ac.acc_words : 0);
-  const int tid = dr_tid<ACC>();
+  // (ACC, IG: the body runs in a loop; an opaque tid keeps what derives from it out of registers held over the loop)
+  const int tid = dr_tid<ACC || IG>();
   const int lane = tid & 63;
-  const int wave = dr_wave<ACC>(tid);
+  const int wave = dr_wave<ACC || IG>(tid);
   const int b = ACC ? ac.gi : (int)blockIdx.x;
   const dr_graph_store& s = a.s;
   // one 64-byte scalar load (ACC: spelled out — in the accumulating kernel's
@@ -1229,6 +1240,32 @@ __device__ __forceinline__ uint64_t graph_body(const GinetArgs& a, const AccCtx&
       // this wave's Z rows are complete in LDS before its own MFMA reads them
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       }  // (ZIN: Z was staged whole, before the barrier)
+      if (IG) {
+        // columns 0 .. KPT - 1 (all the MFMA and the tail read), one 16-byte chunk
+        // per lane and round; Zb straight from the array (L2-resident, read once per step)
+        constexpr int CH = KPT / 4;
+        const float al = ac.ig_alpha;
+        for (int p = lane; p < 16 * CH; p += 64) {
+          const int row = r0 + p / CH, ch = p % CH;
+          if (row < N) {
+            float4* zp = reinterpret_cast<float4*>(sZ + row * LDW + ch * 4);
+            float4 v = *zp;
+            if (ac.ig_zb) {
+              const float4 zb = *reinterpret_cast<const float4*>(ac.ig_zb + (n0 + row) * (int64_t)LDW + ch * 4);
+              v.x = fmaf(al, v.x - zb.x, zb.x);
+              v.y = fmaf(al, v.y - zb.y, zb.y);
+              v.z = fmaf(al, v.z - zb.z, zb.z);
+              v.w = fmaf(al, v.w - zb.w, zb.w);
+            } else {
+              v.x *= al;
+              v.y *= al;
+              v.z *= al;
+              v.w *= al;
+            }
+            *zp = v;
+          }
+        }
+      }
       if (tt == 0) STAMP(20);  // (wave 0's first tile: gather done)
       const int ar = min(r0 + li, N - 1);  // rows past N compute garbage that is never pooled
       floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -1420,6 +1457,196 @@ __global__ void __launch_bounds__(NT) ginet_input_grad_kernel(GinetArgs a, dr_in
       *reinterpret_cast<float4*>(row + ch * 4) = acc;
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// Integrated gradients (dr_ginet_integrated_grad_pass):
+//   attr = (x - xb) . sum_s w_s g_s,  g_s = d(out . dout) / dx at xb + alpha_s (x - xb).
+// Z = A x is linear in x, so step s is the Z-input pass on the graph's Z block
+// rescaled to Zb + alpha_s (Z - Zb) (graph_body<..., IG>), followed by
+// ginet_input_grad_kernel's dZ chain with dp1 weighted by w_s; dX = A^T dZ is
+// linear too, so the steps' dZ are summed in LDS (dZacc) and the transposed
+// gather runs once.  Workgroup (b, g) runs graph b over the steps
+// [g S / G, (g + 1) S / G) in ascending order and writes its sum to its own
+// rows of part[g]; ig_finish_kernel adds the groups' rows.  The training
+// pass's slab / head / out writes go to group g's own scratch rows: no word is
+// written by two workgroups.  LDS: the Z-form input-gradient layout (the
+// transposed CSR behind the carve), then dZacc, N rows of r4(F) words.
+// ---------------------------------------------------------------------------
+struct IntGradLds {
+  int trp, tcol, dz, total;
+};
+__host__ __device__ inline IntGradLds intgrad_lds(const Carve& c, int N, int E, int zs) {
+  const IgLds g = ig_lds(c, N, E, zs);
+  IntGradLds t;
+  t.trp = g.trp;
+  t.tcol = g.tcol;
+  t.dz = g.total;
+  t.total = t.dz + r4(N * c.XS);
+  return t;
+}
+
+struct IntGradArgs {
+  GinetArgs a;
+  dr_integrated_grad ig;
+};
+// What the kernel's own phases need of a graph's LDS, re-derived from the
+// descriptor around every pass instead of being held in registers over it
+struct IntGradView {
+  int N, E, K0, DS;
+  float* dZ;
+  int* trp;
+  uint16_t* tcol;
+  const float* dp1;
+  const int* a1;
+};
+__device__ __forceinline__ IntGradView intgrad_view(const GinetArgs& a, const dr_graph_desc& d, float* lds) {
+  const Carve c = carve(d.n_nodes, d.n_edges, a.s.n_feat, d.n_k0, d.n_p1, d.n_k1, a.s.transpose_aliased, a.p.out_dim, a.z_stride);
+  const IntGradLds g = intgrad_lds(c, d.n_nodes, d.n_edges, a.z_stride);
+  IntGradView v;
+  v.N = d.n_nodes;
+  v.E = d.n_edges;
+  v.K0 = d.n_k0;
+  v.DS = c.XS;
+  v.dZ = lds + g.dz;
+  v.trp = reinterpret_cast<int*>(lds + g.trp);
+  v.tcol = reinterpret_cast<uint16_t*>(lds + g.tcol);
+  v.dp1 = lds + c.dp1;
+  v.a1 = reinterpret_cast<const int*>(lds + c.a1);
+  return v;
+}
+
+template <int KPT>
+__global__ void __launch_bounds__(NT) ginet_integrated_grad_kernel(IntGradArgs ia) {
+  extern __shared__ __attribute__((aligned(16))) float lds_raw[];
+  float* lds = lds_raw;
+  // every phase reads the arguments from the kernarg segment through a pointer
+  // the optimiser cannot follow (as ginet_acc_kernel's loop does): scalar
+  // loads of what the phase uses, nothing held in SGPRs over the passes
+  auto kargs = []() {
+    typedef const __attribute__((address_space(4))) IntGradArgs* KArgs;
+    KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("; dr_kargs" : "+s"(ka));
+    return (const IntGradArgs*)ka;
+  };
+  const int b = blockIdx.x, grp = blockIdx.y;
+  {
+    const IntGradArgs* ka = kargs();
+    const int tid = dr_tid<true>();
+    const dr_graph_desc d = desc_scalar(ka->a.descs + b);
+    const IntGradView v = intgrad_view(ka->a, d, lds);
+    // behind the carve, so no pass touches them: zeroed / copied once (the first
+    // pass's staging wait and barrier cover both)
+    for (int p = tid; p < v.N * v.DS; p += NT) v.dZ[p] = 0.f;
+    dma_copy<NT, 4>(v.trp, ka->a.s.t_rowptr + d.node0 + d.gid, v.N + 1, tid);
+    dma_copy<NT, 16>(v.tcol, ka->a.s.t_col + d.col0, (v.E + 7) / 8, tid, 7);
+  }
+  const int s0 = (int)((int64_t)grp * ia.ig.n_steps / ia.ig.n_groups);
+  const int s1 = (int)((int64_t)(grp + 1) * ia.ig.n_steps / ia.ig.n_groups);
+  for (int s = s0; s < s1; ++s) {
+    {
+      const IntGradArgs* ka = kargs();
+      GinetArgs a = ka->a;
+      const int F = a.s.n_feat, OUT = a.p.out_dim;
+      // this group's rows of the training pass's outputs
+      a.p.slab = ka->ig.slab + (int64_t)grp * a.B * DR_SLAB_STRIDE(F);
+      a.p.head = ka->ig.head + (int64_t)grp * a.B * DR_HEAD_STRIDE(OUT);
+      a.p.out = ka->ig.out + (int64_t)grp * a.B * OUT;
+      AccCtx ac;
+      typedef const __attribute__((address_space(4))) float* CF32;
+      ac.ig_alpha = *(CF32)(ka->ig.alpha + s);
+      ac.ig_zb = ka->ig.zb;
+      graph_body<KPT, false, false, true, false, true>(a, ac);
+    }
+    __syncthreads();  // the tail's last step (dW1) has read Z; dp1 / a1 are complete
+    {
+      // ginet_input_grad_kernel's chain, dp1 weighted by w_s, into the running
+      // dZacc: one thread per (cluster, feature), channels ascending.  (Written
+      // out here and in that kernel: called from one helper, with the gather,
+      // that kernel's VGPR and SGPR-spill figures moved: 91 -> 89, 42 -> 43.)
+      const IntGradArgs* ka = kargs();
+      const int tid = dr_tid<true>();
+      const IntGradView v = intgrad_view(ka->a, desc_scalar(ka->a.descs + b), lds);
+      const int F = ka->a.s.n_feat, N = v.N, DS = v.DS;
+      typedef const __attribute__((address_space(4))) float* CF32;
+      const float ws = *(CF32)(ka->ig.weight + s);
+      for (int p = tid; p < v.K0 * F; p += NT) {
+        const int k = p / F, f = p - k * F;
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+          const float* wsrc = (hf ? ka->a.w.w1e : ka->a.w.w1) + f;
+          float w[16], dv[16];
+          int i[16];
+#pragma unroll
+          for (int u = 0; u < 16; ++u) w[u] = wsrc[u * F];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int4 iv = *reinterpret_cast<const int4*>(v.a1 + k * 32 + hf * 16 + 4 * q);
+            const float4 vv = *reinterpret_cast<const float4*>(v.dp1 + k * 32 + hf * 16 + 4 * q);
+            i[4 * q] = iv.x; i[4 * q + 1] = iv.y; i[4 * q + 2] = iv.z; i[4 * q + 3] = iv.w;
+            dv[4 * q] = ws * vv.x; dv[4 * q + 1] = ws * vv.y; dv[4 * q + 2] = ws * vv.z; dv[4 * q + 3] = ws * vv.w;
+          }
+#pragma unroll
+          for (int u = 0; u < 16; ++u)
+            if (i[u] < N) v.dZ[i[u] * DS + f] = fmaf(dv[u], w[u], v.dZ[i[u] * DS + f]);
+        }
+      }
+    }
+    __syncthreads();  // the chain has read dp1 / a1 before the next step's staging and zeroing
+  }
+  // part[g][m, :] = sum over transposed row m, in slot order from +0, of dZacc[t_col[s], :]
+  const IntGradArgs* ka = kargs();
+  const int tid = dr_tid<true>();
+  const IntGradView v = intgrad_view(ka->a, desc_scalar(ka->a.descs + b), lds);
+  const int DXS = ka->ig.dx_stride;
+  const int sub = tid & 7, nchd = v.DS >> 2, ncho = DXS >> 2;
+  typedef const __attribute__((address_space(4))) int64_t* CI64;
+  float* prow0 = ka->ig.part + ((int64_t)grp * ka->ig.part_rows + *(CI64)(ka->ig.part_off + b)) * (int64_t)DXS;
+  for (int m = tid >> 3; m < v.N; m += NT / 8) {
+    const int eb = v.trp[m], ee = v.trp[m + 1];
+    float* row = prow0 + m * (int64_t)DXS;
+    for (int ch = sub; ch < ncho; ch += 8) {
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (ch < nchd) acc = drk::gather_row_chunk_lds(v.tcol, eb, ee, v.dZ, v.DS, ch * 4);
+      *reinterpret_cast<float4*>(row + ch * 4) = acc;
+    }
+  }
+}
+
+// attr = (x - xb) . (part[0] + part[1] + ... + part[G - 1]), the groups summed
+// ascending from +0, zeros in columns F .. dx_stride - 1, and attr_sum[b] =
+// the graph's sum of attr in fp64: each thread sums its elements in ascending
+// order, then a fixed tree over the 256 threads (no atomics: equal bits on
+// every call).  One workgroup per graph.
+constexpr int NTF = 256;
+__global__ void __launch_bounds__(NTF) ig_finish_kernel(dr_graph_store s, const dr_graph_desc* descs, dr_integrated_grad ig) {
+  __shared__ double red[NTF];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const dr_graph_desc d = descs[b];
+  const int N = d.n_nodes, F = s.n_feat, DXS = ig.dx_stride;
+  const int64_t arow0 = ig.row_off[b], prow0 = ig.part_off[b], gstride = ig.part_rows * (int64_t)DXS;
+  double acc = 0.0;
+  for (int p = tid; p < N * DXS; p += NTF) {
+    const int m = p / DXS, f = p - m * DXS;
+    float v = 0.f;
+    if (f < F) {
+      const float* pp = ig.part + (prow0 + m) * (int64_t)DXS + f;
+      float sum = 0.f;
+      for (int g = 0; g < ig.n_groups; ++g) sum += pp[g * gstride];
+      float dxv = s.x[(d.node0 + m) * (int64_t)s.x_stride + f];
+      if (ig.xb) dxv -= ig.xb[(d.node0 + m) * (int64_t)s.x_stride + f];
+      v = dxv * sum;
+      acc += (double)v;
+    }
+    ig.attr[(arow0 + m) * (int64_t)DXS + f] = v;
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int h = NTF / 2; h > 0; h >>= 1) {
+    if (tid < h) red[tid] += red[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) ig.attr_sum[b] = red[0];
 }
 
 // ---------------------------------------------------------------------------
@@ -2287,6 +2514,61 @@ extern "C" int dr_ginet_input_grad_pass(const dr_graph_store* store, const dr_gr
   });
 }
 
+extern "C" int64_t dr_ginet_integrated_grad_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t n_feat, int32_t k0,
+                                                      int32_t p1_edges, int32_t k1, int32_t transpose_aliased,
+                                                      int32_t out_dim, int32_t z_stride) {
+  if (z_stride < (n_feat <= 32 ? 32 : 64)) return -1;  // (no gather form: a Z stride is required)
+  const Carve c = carve(n_nodes, n_edges, n_feat, k0, p1_edges, k1, transpose_aliased, out_dim, z_stride);
+  return 4LL * intgrad_lds(c, n_nodes, n_edges, z_stride).total;
+}
+
+extern "C" int dr_ginet_integrated_grad_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                                             const dr_ginet_weights* w, const dr_pass* pass, const dr_integrated_grad* ig,
+                                             const float* z, int32_t z_stride, int32_t lds_bytes, void* stream) {
+  if (!pass || !ig) return DR_E_ARG;
+  dr_pass gp = *pass;  // the pass as the steps run it: its partials go to the groups' scratch rows
+  gp.slab = ig->slab;
+  gp.head = ig->head;
+  gp.out = ig->out;
+  gp.loss_per_graph = nullptr;  // (one word per graph, which the groups would all write)
+  gp.stamps = nullptr;
+  DR_CHECK(graph_pass_check(store, descs, n_batch, w, &gp, lds_bytes));
+  if (!(pass->flags & DR_PASS_BACKWARD)) return DR_E_ARG;
+  if (pass->slot || pass->step_counter) return DR_E_ARG;
+  if (!ig->attr || !ig->row_off || !ig->alpha || !ig->weight || !ig->part || !ig->part_off || !ig->attr_sum ||
+      !ig->slab || !ig->head || !ig->out)
+    return DR_E_ARG;
+  if (ig->n_steps < 1 || ig->n_groups < 1 || ig->n_groups > ig->n_steps) return DR_E_ARG;
+  if (ig->dx_stride < store->n_feat || ig->dx_stride % 4 != 0) return DR_E_ARG;
+  if (reinterpret_cast<uintptr_t>(ig->attr) % 16 != 0 || reinterpret_cast<uintptr_t>(ig->part) % 16 != 0) return DR_E_ARG;
+  if (ig->part_rows < 0) return DR_E_ARG;
+  if ((ig->zb != nullptr) != (ig->xb != nullptr)) return DR_E_ARG;
+  // no gather form; the steps rescale Z in 16-byte chunks (rows of z and zb a multiple of 4 words, 16-byte aligned)
+  if (!z_args_ok(store, z, z_stride) || z_stride % 4 != 0) return DR_E_ARG;
+  if (reinterpret_cast<uintptr_t>(z) % 16 != 0 || reinterpret_cast<uintptr_t>(ig->zb) % 16 != 0) return DR_E_ARG;
+  if (n_batch == 0) return DR_OK;
+  if (!store->cl0 || !store->t_rowptr || !store->t_col || !store->x) return DR_E_ARG;
+  IntGradArgs ia;
+  GinetArgs& args = ia.a;
+  args.s = *store;
+  args.w = *w;
+  args.p = gp;
+  args.descs = descs;
+  args.B = n_batch;
+  args.z = z;
+  args.z_stride = z_stride;
+  ia.ig = *ig;
+  const auto launch = [&](auto kpt) {
+    const auto kernel = &ginet_integrated_grad_kernel<decltype(kpt)::value>;
+    DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(kernel)));
+    hipLaunchKernelGGL(kernel, dim3(n_batch, ia.ig.n_groups), dim3(NT), lds_bytes, (hipStream_t)stream, ia);
+    return (int)hipGetLastError();
+  };
+  DR_CHECK(store->n_feat <= 32 ? launch(std::integral_constant<int, 32>()) : launch(std::integral_constant<int, 64>()));
+  hipLaunchKernelGGL(ig_finish_kernel, dim3(n_batch), dim3(NTF), 0, (hipStream_t)stream, args.s, descs, ia.ig);
+  return (int)hipGetLastError();
+}
+
 extern "C" int dr_ginet_multi_pass(const dr_graph_store* store, const dr_ginet_member* members, int32_t n_members,
                                    int32_t lds_bytes, const float* z, int32_t z_stride, void* stream) {
   if (!store || !members || n_members < 1 || n_members > DR_MAX_MEMBERS) return DR_E_ARG;
@@ -2679,6 +2961,21 @@ extern "C" int dr_debug_carve_ginet_ig(const int32_t* q, char* buf, int32_t len)
   describe_carve(d, c);
   DR_DESC(d, g, trp);
   DR_DESC(d, g, tcol);
+  dr_carve_put(d, "$carve_total", c.total);
+  DR_DESC(d, g, total);
+  return d.pos;
+}
+
+// the integrated-gradient kernel's LDS: the Z-form carve, the transposed CSR
+// and the running dZ sum; q: N, E, F, K0, P1, K1, alias, OUT, zs (> 0)
+extern "C" int dr_debug_carve_ginet_intgrad(const int32_t* q, char* buf, int32_t len) {
+  const Carve c = carve(q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8]);
+  const IntGradLds g = intgrad_lds(c, q[0], q[1], q[8]);
+  DrCarveDesc d{buf, len, 0};
+  describe_carve(d, c);
+  DR_DESC(d, g, trp);
+  DR_DESC(d, g, tcol);
+  DR_DESC(d, g, dz);
   dr_carve_put(d, "$carve_total", c.total);
   DR_DESC(d, g, total);
   return d.pos;

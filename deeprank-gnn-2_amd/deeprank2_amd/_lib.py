@@ -246,6 +246,14 @@ class InputGradC(ctypes.Structure):
     _fields_ = [("dx", VP), ("row_off", VP), ("dx_stride", ctypes.c_int32), ("pad0", ctypes.c_int32)]
 
 
+class IntegratedGradC(ctypes.Structure):
+    """dr_integrated_grad: the quadrature, the baseline, the outputs and the scratch of dr_ginet_integrated_grad_pass."""
+
+    _fields_ = [("attr", VP), ("row_off", VP), ("dx_stride", ctypes.c_int32), ("n_steps", ctypes.c_int32), ("n_groups", ctypes.c_int32), ("pad0", ctypes.c_int32),
+                ("alpha", VP), ("weight", VP), ("zb", VP), ("xb", VP), ("part", VP), ("part_off", VP), ("part_rows", ctypes.c_int64),
+                ("attr_sum", VP), ("slab", VP), ("head", VP), ("out", VP)]  # fmt: skip
+
+
 class ReduceMemberC(ctypes.Structure):
     """dr_reduce_member: what dr_reduce_update_opt takes, for one model of dr_reduce_multi_build."""
 
@@ -271,6 +279,8 @@ SIGNATURES = [
     ("dr_debug_graph_record", ctypes.c_int, [_c_i32, _c_i32]),
     ("dr_ginet_input_grad_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.POINTER(InputGradC), VP, ctypes.c_int32, ctypes.c_int32, VP]),
     ("dr_ginet_input_grad_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 9),
+    ("dr_ginet_integrated_grad_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.POINTER(IntegratedGradC), VP, ctypes.c_int32, ctypes.c_int32, VP]),
+    ("dr_ginet_integrated_grad_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 9),
     ("dr_ginet_multi_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), ctypes.POINTER(GinetMemberC), ctypes.c_int32, ctypes.c_int32, VP, ctypes.c_int32, VP]),
     ("dr_reduce_multi_args_bytes", ctypes.c_int64, [ctypes.c_int32]),
     ("dr_reduce_multi_build", ctypes.c_int, [ctypes.POINTER(ReduceMemberC), ctypes.c_int32, VP, ctypes.c_int64]),
@@ -322,7 +332,7 @@ SIGNATURES = [
     ("dr_mcl", ctypes.c_int, [ctypes.POINTER(MclGraphsC), ctypes.c_int32, ctypes.c_int32, ctypes.c_double, VP]),
     ("dr_mcl_assign", ctypes.c_int, [VP, VP, VP, ctypes.c_int32, VP, VP]),
     ("dr_dropout_mask", ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int32, ctypes.c_float, VP]),
-    *[(f"dr_debug_carve_{k}", ctypes.c_int, [VP, ctypes.c_char_p, ctypes.c_int32]) for k in ("ginet", "ginet_z", "ginet_acc", "ginet_ig", "ginet_conv", "ginet_conv_bf16", "ginet_tail", "fout", "fout_conv", "fout_tail", "nocluster", "vanilla_graph", "vanilla_tile", "vanilla_chunk_fwd", "vanilla_chunk_bwd")],
+    *[(f"dr_debug_carve_{k}", ctypes.c_int, [VP, ctypes.c_char_p, ctypes.c_int32]) for k in ("ginet", "ginet_z", "ginet_acc", "ginet_ig", "ginet_intgrad", "ginet_conv", "ginet_conv_bf16", "ginet_tail", "fout", "fout_conv", "fout_tail", "nocluster", "vanilla_graph", "vanilla_tile", "vanilla_chunk_fwd", "vanilla_chunk_bwd")],
     ("dr_debug_xcd_tile", ctypes.c_int, [ctypes.c_int32, VP]),
     ("dr_version", ctypes.c_char_p, []),
     ("dr_device_arch", ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32]),

@@ -20,6 +20,9 @@
  *                           (deeprank2/trainer.py:686-689)
  *   dr_ginet_input_grad_pass  torch.autograd.grad((model(batch) * seed).sum(), batch.x)
  *                           on GINet (ginet.py:40-60,90-125): per-node attribution
+ *   dr_ginet_integrated_grad_pass  S such torch.autograd.grad calls along the path
+ *                           from a baseline to x, weighted and summed (integrated
+ *                           gradients; the reference has no attribution call)
  *   dr_fout_graph_pass      FoutNet.forward + autograd backward
  *                           (deeprank2/neuralnets/gnn/foutnet.py:48-66,99-118)
  *                           plus the same loss gradient
@@ -394,6 +397,69 @@ int dr_ginet_input_grad_pass(const dr_graph_store* store, const dr_graph_desc* d
 int64_t dr_ginet_input_grad_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t n_feat, int32_t k0,
                                       int32_t p1_edges, int32_t k1, int32_t transpose_aliased, int32_t out_dim,
                                       int32_t z_stride);
+
+/* ---- GINet integrated gradients (Sundararajan et al. 2017) -----------------
+ * Replaces S calls of torch.autograd.grad((model(batch(alpha_s)) * seed).sum(),
+ * batch.x) on the reference GINet (ginet.py:40-60,90-125), weighted and summed
+ * by the caller; the reference has no attribution call of its own.  For nodes
+ * alpha_s in [0, 1] and weights w_s (sum 1), s = 0 .. n_steps - 1:
+ *   attr[i, f] = (x[i, f] - xb[i, f]) * sum_s w_s g_s[i, f]
+ *   g_s        = d (out(x_s) . dout) / dx  at  x_s = xb + alpha_s (x - xb)
+ * in eval mode.  Conv1 aggregates first and Z = A x is linear in x, so step s
+ * is dr_ginet_graph_pass_z's pass on Z_s = Zb + alpha_s (Z - Zb), Zb = A xb (a
+ * zero baseline: Z_s = alpha_s Z), formed in LDS from the staged Z block; then
+ * dr_ginet_input_grad_pass's dZ chain with dp1 weighted by w_s adds to a sum
+ * kept in LDS, and dX = A^T dZ, linear too, is gathered once per workgroup.
+ * Launch 1, grid (n_batch, n_groups): workgroup (b, g) runs graph b over the
+ * steps [g S / G, (g + 1) S / G) (integer floors), ascending, and writes its
+ * sum to rows part_off[b] .. of part[g] ([n_groups, part_rows, dx_stride]).
+ * Launch 2, one workgroup per graph: attr = (x - xb) * (part[0] + part[1] + ..
+ * + part[G - 1]) added in that order from +0, zeros in columns F .. dx_stride -
+ * 1, and attr_sum[b] = the graph's sum of attr in fp64, reduced in a fixed
+ * order.  No atomics anywhere and no word written by two workgroups: repeated
+ * calls give equal bits.  With n_steps = n_groups = 1, alpha = {1}, weight =
+ * {1} and no baseline, attr is x times dr_ginet_input_grad_pass's dx bit for bit.
+ * The outputs at x and at xb are not this entry's: run dr_ginet_graph_pass_z on
+ * z and on zb.  The training pass each step runs writes its slab / head / out
+ * partials to group g's own rows of the scratch arrays below (pass->slab, head,
+ * out, loss_per_graph and stamps are not used); pass->dout is the seed.
+ * z, z_stride: the store's Z = A x (dr_aggregate_x), required (there is no
+ * gather form), rows a multiple of 4 words and 16-byte aligned, as zb's.
+ * lds_bytes: dr_ginet_integrated_grad_lds_bytes of the batch's largest graph =
+ * dr_ginet_input_grad_lds_bytes' Z-form value + 4 r4(N r4(F)); -1 for a
+ * z_stride below the kernel's K.
+ * DR_E_ARG: a NULL ig or a NULL attr, row_off, alpha, weight, part, part_off,
+ * attr_sum, slab, head or out; n_steps < 1; n_groups < 1 or > n_steps; attr or
+ * part not 16-byte aligned; a dx_stride below F or not a multiple of 4; z NULL
+ * or unusable; zb without xb or xb without zb; a pass without DR_PASS_BACKWARD;
+ * a non-NULL pass->slot or pass->step_counter.  DR_E_UNSUPPORTED: compute_dtype
+ * != DR_DTYPE_F32.  n_batch == 0: DR_OK, nothing launched.  No allocation, no
+ * host synchronisation: capturable.                                          */
+typedef struct dr_integrated_grad {
+  float* attr;             /* [rows, dx_stride] fp32, 16-byte aligned rows              */
+  const int64_t* row_off;  /* device [B]: first attr row of launch position b's graph   */
+  int32_t dx_stride;       /* multiple of 4, >= F; the row stride of attr and part      */
+  int32_t n_steps;         /* S                                                         */
+  int32_t n_groups;        /* G: workgroups per graph, 1 .. S                           */
+  int32_t pad0;
+  const float* alpha;      /* device fp32 [S]: the quadrature nodes                     */
+  const float* weight;     /* device fp32 [S]: the quadrature weights                   */
+  const float* zb;         /* [N_all, z_stride] A xb in z's layout, or NULL (zero baseline) */
+  const float* xb;         /* [N_all, x_stride] the baseline in x's layout, or NULL     */
+  float* part;             /* scratch [G, part_rows, dx_stride], 16-byte aligned        */
+  const int64_t* part_off; /* device [B]: graph b's first row inside a group's part rows */
+  int64_t part_rows;       /* rows per group: at least the batch's node count           */
+  double* attr_sum;        /* device fp64 [B]                                           */
+  float* slab;             /* scratch [G, B, DR_SLAB_STRIDE(F)]                         */
+  float* head;             /* scratch [G, B, DR_HEAD_STRIDE(out)]                       */
+  float* out;              /* scratch [G, B, out]                                       */
+} dr_integrated_grad;
+int dr_ginet_integrated_grad_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                                  const dr_ginet_weights* w, const dr_pass* pass, const dr_integrated_grad* ig,
+                                  const float* z, int32_t z_stride, int32_t lds_bytes, void* stream);
+int64_t dr_ginet_integrated_grad_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t n_feat, int32_t k0,
+                                           int32_t p1_edges, int32_t k1, int32_t transpose_aliased, int32_t out_dim,
+                                           int32_t z_stride);
 
 /* Up to DR_MAX_MEMBERS independent GINet models (an ensemble, the folds of a
  * cross-validation, a hyper-parameter sweep) over ONE store in ONE launch:
@@ -1107,6 +1173,9 @@ int dr_debug_carve_ginet_acc(const int32_t* q, char* buf, int32_t len);
 /* dr_ginet_input_grad_lds_bytes' arguments: the per-graph carve, then the
  * transposed CSR ("trp", "tcol"); "$carve_total": the carve's own words. */
 int dr_debug_carve_ginet_ig(const int32_t* q, char* buf, int32_t len);
+/* dr_ginet_integrated_grad_lds_bytes' arguments (z_stride > 0): the Z-form
+ * carve, the transposed CSR ("trp", "tcol") and the running dZ sum ("dz"). */
+int dr_debug_carve_ginet_intgrad(const int32_t* q, char* buf, int32_t len);
 int dr_debug_carve_ginet_conv(const int32_t* q, char* buf, int32_t len);
 int dr_debug_carve_ginet_conv_bf16(const int32_t* q, char* buf, int32_t len);
 int dr_debug_carve_ginet_tail(const int32_t* q, char* buf, int32_t len);

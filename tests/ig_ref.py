@@ -1,0 +1,158 @@
+"""TEST INFRASTRUCTURE: the CPU reference of GINet integrated gradients, and
+the named batches, baselines and targets the host and GPU tests share.
+
+The reference is the oracle model (``oracle/gnn_ref.GINet``) in eval mode, run
+in float64 (``torch.set_default_dtype`` around the calls, as
+``width_cases.py`` does), on ``attribution_ref.grad_batch`` batches:
+
+    attr = (x - b) * sum_s w_s g_s,   g_s = d (out(x_s) . seed) / dx at x_s = b + alpha_s (x - b)
+
+with ``alpha`` / ``w`` the fp32 roundings of ``attribution.quadrature`` — the
+numbers the device gets.  ``"pred"`` is decided once, from the forward at x.
+
+Tolerances (the suite's): outputs rtol = atol = 1e-4; attributions
+``_util.assert_grad_close`` per graph (rtol 1e-4, floor 1e-6 max|ref|, at least
+1e-6); a graph's ``attr_sum`` and ``delta`` that element tolerance summed,
+
+    |got - ref| <= 1e-4 sum|attr_ref| + N F max(1e-6, 1e-6 max|attr_ref|).
+"""
+
+from __future__ import annotations
+
+import copy
+import functools
+
+import numpy as np
+import torch
+
+import attribution_ref
+import graph_zoo
+from deeprank2_amd import attribution
+from deeprank2_amd.utils.synthetic import make_dataset
+from oracle import data_ref, gnn_ref
+
+TOL = dict(rtol=1e-4, atol=1e-4)
+BATCHES = ("asym", "deg", "f33", "f12")
+BASELINES = ("zero", "mean")
+# target name -> (out_dim, target)
+TARGETS = {"one": (1, None), "t1": (2, 1), "pred": (2, "pred"), "seed": (2, "seed")}
+
+
+def _synthetic(n_feat, seed):
+    """``test_gpu_attribution._synthetic``: four synthetic graphs with seeded
+    normal features (no ties between the members of a cluster)."""
+    graphs = make_dataset(4, seed=seed, n_lo=20, n_hi=90, mean_degree=6.0, k_lo=2, k_hi=14, n_feat=n_feat)
+    rng = np.random.default_rng(seed)
+    for g in graphs:
+        g["x"] = rng.normal(size=g["x"].shape).astype(np.float32)
+    return tuple(data_ref.synthetic_to_data(g, f"f{n_feat}_{j}") for j, g in enumerate(graphs))
+
+
+@functools.lru_cache(maxsize=None)
+def datas(batch):
+    if batch == "asym":
+        return tuple(graph_zoo.asymmetric(**graph_zoo.ASYM_BATCH))
+    if batch == "deg":
+        return tuple(graph_zoo.degenerate())
+    if batch == "f33":
+        return _synthetic(33, 71)
+    assert batch == "f12"
+    return _synthetic(12, 72)
+
+
+def n_feat(batch):
+    return {"f33": 33, "f12": 12}.get(batch, 30)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_model(nf, out_dim):
+    torch.manual_seed(11)
+    return gnn_ref.GINet(nf, out_dim, 3).eval()
+
+
+def target_of(batch, name):
+    out_dim, target = TARGETS[name]
+    if target == "seed":
+        target = torch.randn(len(datas(batch)), out_dim, generator=torch.Generator().manual_seed(5))
+    return out_dim, target
+
+
+@functools.lru_cache(maxsize=None)
+def baseline_of(batch, kind):
+    """None (zeros) or the per-feature mean over the batch's nodes, fp32 ``[F]``."""
+    if kind == "zero":
+        return None
+    assert kind == "mean"
+    return torch.cat([d.x for d in datas(batch)]).mean(dim=0).to(torch.float32)
+
+
+def nodes(steps, method="gausslegendre"):
+    """The quadrature as the device gets it: fp32 roundings."""
+    a, w = attribution.quadrature(method, steps)
+    return a.astype(np.float32), w.astype(np.float32)
+
+
+def integrated_gradients(model_o, ds, target, alpha, weight, baseline=None, dtype=torch.float64):
+    """The oracle's integrated gradients on the graphs ``ds`` as a dict of
+    numpy arrays in ``dtype``: out, out_baseline [n, out_dim], attr [rows, F],
+    seed, attr_sum, delta [n], node_off [n + 1].  ``baseline``: None, ``[F]``
+    or ``[rows, F]``; ``alpha`` / ``weight``: the nodes and weights, used as given."""
+    assert not model_o.training
+    model = copy.deepcopy(model_o).to(dtype)
+    torch.set_default_dtype(dtype)  # oracle/pyg_ops.py and the layers allocate in the default dtype
+    try:
+
+        def fresh():  # (the oracle's forward rewrites its batch in place)
+            bat = attribution_ref.grad_batch(list(ds))
+            for k in ("x", "edge_attr", "pos", "y"):
+                if getattr(bat, k, None) is not None:
+                    setattr(bat, k, getattr(bat, k).to(dtype))
+            return bat
+
+        x = fresh().x.clone()
+        b = torch.zeros_like(x) if baseline is None else torch.as_tensor(baseline).to(dtype).expand_as(x).clone()
+
+        def forward(xs):
+            bat = fresh()
+            bat.x = xs
+            return model(bat)
+
+        with torch.no_grad():
+            out, out_b = forward(x.clone()), forward(b.clone())
+        seed = attribution_ref.seed_for(out, target, out.shape[0], out.shape[1]).to(dtype)
+        acc = torch.zeros_like(x)
+        for a_s, w_s in zip(alpha, weight):
+            xs = (b + float(a_s) * (x - b)).requires_grad_()
+            (g,) = torch.autograd.grad((forward(xs) * seed).sum(), xs)
+            acc += float(w_s) * g
+        attr = (x - b) * acc
+    finally:
+        torch.set_default_dtype(torch.float32)
+    node_off = np.concatenate([[0], np.cumsum([d.x.shape[0] for d in ds])]).astype(np.int64)
+    attr = attr.numpy()
+    attr_sum = np.array([attr[node_off[g] : node_off[g + 1]].astype(np.float64).sum() for g in range(len(ds))])
+    out, out_b, seed = out.numpy(), out_b.numpy(), seed.numpy()
+    delta = attr_sum - ((out.astype(np.float64) - out_b) * seed).sum(axis=1)
+    return {"out": out, "out_baseline": out_b, "attr": attr, "seed": seed, "attr_sum": attr_sum, "delta": delta, "node_off": node_off}
+
+
+@functools.lru_cache(maxsize=None)
+def reference(batch, name="t1", kind="zero", steps=8, method="gausslegendre", dtype=torch.float64):
+    """The oracle's result on a named batch, target and baseline (computed once, shared, unchanged)."""
+    out_dim, target = target_of(batch, name)
+    return integrated_gradients(oracle_model(n_feat(batch), out_dim), datas(batch), target, *nodes(steps, method), baseline_of(batch, kind), dtype)
+
+
+def sum_tolerance(ref, g):
+    """The bound on graph g's ``attr_sum`` and ``delta``: the element tolerance
+    of ``assert_grad_close`` (rtol 1e-4, floor max(1e-6, 1e-6 max|ref|)) summed
+    over the graph's N F attributions."""
+    a = np.abs(ref["attr"][ref["node_off"][g] : ref["node_off"][g + 1]].astype(np.float64))
+    return 1e-4 * a.sum() + a.size * max(1e-6, 1e-6 * (a.max() if a.size else 0.0))
+
+
+def elementwise_excess(got, ref):
+    """max over the entries of |got - ref| / (assert_grad_close's bound): <= 1 passes."""
+    ref = np.asarray(ref, dtype=np.float64)
+    bound = max(1e-6, 1e-6 * float(np.abs(ref).max())) + 1e-4 * np.abs(ref)
+    return float((np.abs(np.asarray(got, dtype=np.float64) - ref) / bound).max())

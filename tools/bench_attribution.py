@@ -24,6 +24,10 @@ and after).  The variants are interleaved in one process and each runs
 ``--runs`` times; the table gives the mean and the spread (max - min).  The
 last lines say whether the fused route beats the layer route by more than five
 times that route's own spread (the bar for keeping it the default).
+
+``--ig`` measures integrated gradients instead (``main_ig``: the bare
+``dr_ginet_integrated_grad_pass`` for each group count, the public call, and
+the layer route as the baseline), by the same rules.
 """
 
 from __future__ import annotations
@@ -69,11 +73,122 @@ def interleaved(variants, runs, reps):
     return times
 
 
+IG_STEPS = 32
+IG_GROUPS = (1, 2, 4, 8, 32)
+
+
+def main_ig(args):
+    """``--ig``: integrated gradients, 32 Gauss-Legendre nodes, zero baseline.
+
+    * ``pass_gG``        the bare ``dr_ginet_integrated_grad_pass`` (both launches)
+                         with G workgroups per graph, G in 1, 2, 4, 8, 32;
+    * ``pass_mean``      the same at the default G with a per-feature mean
+                         baseline: the difference prices the Zb reads;
+    * ``api_fused``      ``integrated_gradients(model, store, batch)``;
+    * ``api_layers``     ``integrated_gradients(..., fused=False)``: 32 times the
+                         layer forward + ``autograd.grad``, the only route the
+                         parent offers: the baseline."""
+    dev = torch.device("cuda:0")
+    store = GraphStore(pack_graphs(records(make_graphs("residue", B, 1000))), dev)
+    torch.manual_seed(0)
+    model = ginet.GINet(30, 1, 3).to(dev).eval()
+    idx = np.arange(B)
+    f, xs, out_dim = store.n_feat, store.x_stride, 1
+
+    def api_fused():
+        return attribution.integrated_gradients(model, store, indices=idx, batch_size=B, steps=IG_STEPS, fused=True)
+
+    def api_layers():
+        return attribution.integrated_gradients(model, store, indices=idx, batch_size=B, steps=IG_STEPS, fused=False)
+
+    a, b = api_fused(), api_layers()
+    assert a.path == "fused" and b.path == "layers"
+    scale = float(b.attr.abs().max())
+    assert torch.allclose(a.attr, b.attr, rtol=1e-4, atol=max(1e-6, 1e-6 * scale)) and torch.allclose(a.out, b.out, rtol=1e-4, atol=1e-4), "the two routes agree"
+    print(f"completeness: max |delta| {float(a.delta.abs().max()):.3e} against a mean sum|attr| of {float(a.attr.abs().sum()) / B:.3e} per graph")
+
+    h = BatchHandle(store, idx.astype(np.int32))
+    params = [p.detach().contiguous() for p in model.ordered_params()]
+    w = ginet.weights_c(params)
+    z, zs = store.agg_x(), store.agg_x_stride
+    lib = _lib.load()
+    stream = _lib.stream_ptr(dev)
+    seed = torch.ones(B, out_dim, device=dev)
+    p = make_pass(out_dim, _lib.DR_PASS_FORWARD | _lib.DR_PASS_BACKWARD, dout=seed)
+    rows = int(a.node_off[-1])
+    attr = torch.empty(rows, xs, device=dev)
+    off = torch.from_numpy(a.node_off[:-1].copy()).to(dev)
+    alpha, weight = torch.from_numpy(a.alpha).to(dev), torch.from_numpy(a.weight).to(dev)
+    attr_sum = torch.empty(B, dtype=torch.float64, device=dev)
+    alias = int(store.packed.transpose_aliased)
+    lds = int(lib.dr_ginet_integrated_grad_lds_bytes(*h.max_sizes[:2], f, *h.max_sizes[2:], alias, out_dim, zs))
+    gmax = max(IG_GROUPS)
+    slab = torch.empty(gmax * B * ginet.slab_stride(f), device=dev)
+    head = torch.zeros(gmax * B * ginet.head_stride(out_dim), device=dev)
+    outs = torch.empty(gmax * B * out_dim, device=dev)
+    part = torch.empty(gmax, rows, xs, device=dev)
+    # the mean baseline in x's layout and its neighbour sums
+    xb = torch.zeros_like(store.x)
+    xb[:, :f] = store.x[:, :f].mean(dim=0)
+    zb = torch.empty_like(z)
+    st = _lib.GraphStoreC.from_buffer_copy(store.cstruct())
+    st.x = xb.data_ptr()
+    _lib.check(lib.dr_aggregate_x(st, zb.data_ptr(), zs, 0, store.n_graphs, stream), "dr_aggregate_x")
+
+    def bare(groups, baseline=False):
+        ig = _lib.IntegratedGradC()
+        ig.attr, ig.row_off, ig.dx_stride = attr.data_ptr(), off.data_ptr(), xs
+        ig.n_steps, ig.n_groups = IG_STEPS, groups
+        ig.alpha, ig.weight = alpha.data_ptr(), weight.data_ptr()
+        ig.zb, ig.xb = (zb.data_ptr(), xb.data_ptr()) if baseline else (None, None)
+        ig.part, ig.part_off, ig.part_rows = part.data_ptr(), off.data_ptr(), rows
+        ig.attr_sum = attr_sum.data_ptr()
+        ig.slab, ig.head, ig.out = slab.data_ptr(), head.data_ptr(), outs.data_ptr()
+
+        def body():
+            _lib.check(lib.dr_ginet_integrated_grad_pass(store.cstruct(), h.descs.data_ptr(), B, w, p, ig, z.data_ptr(), zs, lds, stream), "dr_ginet_integrated_grad_pass")
+
+        return body
+
+    gdef = min(attribution.IG_GROUPS_DEFAULT, IG_STEPS)
+    bare(gdef)()
+    torch.cuda.synchronize()
+    assert torch.equal(attr[:, :f], a.attr), "the bare launch writes the public call's bits"
+
+    variants = {f"pass_g{g}": bare(g) for g in IG_GROUPS}
+    variants["pass_mean"] = bare(gdef, baseline=True)
+    variants["api_fused"] = api_fused
+    variants["api_layers"] = api_layers
+    times = interleaved(variants, args.runs, args.reps)
+    rows_j = []
+    print(f"{'variant':>12} {'us/batch':>10} {'spread us':>10}  runs")
+    for name, ts in times.items():
+        mean, spread = float(np.mean(ts)), float(max(ts) - min(ts))
+        rows_j.append({"variant": name, "us": round(mean, 2), "spread_us": round(spread, 2), "runs_us": [round(x, 2) for x in ts]})
+        print(f"{name:>12} {mean:10.1f} {spread:10.1f}  {' '.join(f'{x:.1f}' for x in ts)}")
+    best = min(IG_GROUPS, key=lambda g: np.mean(times[f"pass_g{g}"]))
+    print(f"fastest groups: {best} (the default is {attribution.IG_GROUPS_DEFAULT})")
+    step_us = float(np.mean(times["pass_g1"])) / IG_STEPS
+    zb_us = float(np.mean(times["pass_mean"]) - np.mean(times[f"pass_g{gdef}"]))
+    print(f"per step, one workgroup per graph (pass_g1 / {IG_STEPS}): {step_us:.2f} us")
+    print(f"Zb reads (pass_mean - pass_g{gdef}): {zb_us:.2f} us per batch, {100 * zb_us / float(np.mean(times['pass_mean'])):.1f} % of pass_mean")
+    n_, o_ = times["api_fused"], times["api_layers"]
+    margin = 5 * (max(o_) - min(o_))
+    wins = bool(np.mean(o_) - np.mean(n_) > margin)
+    print(f"api_fused {np.mean(n_):.1f} us against api_layers {np.mean(o_):.1f} us, 5 x the baseline's spread {margin:.1f} us -> {'fused wins' if wins else 'no win'}")
+    print(json.dumps({"bench": "integrated_gradients", "B": B, "steps": IG_STEPS, "reps": args.reps, "runs": args.runs, "rows": rows_j, "fastest_groups": best, "default_groups": attribution.IG_GROUPS_DEFAULT,
+                      "step_us": round(step_us, 2), "zb_us": round(zb_us, 2), "fused_wins": wins, "five_spreads_us": round(margin, 2)}))  # fmt: skip
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reps", type=int, default=200, help="calls per timing (200: the layer route's timing window is over a second)")
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--ig", action="store_true", help="measure integrated gradients (main_ig) instead of the input gradients")
     args = ap.parse_args()
+    if args.ig:
+        main_ig(args)
+        return
     dev = torch.device("cuda:0")
     store = GraphStore(pack_graphs(records(make_graphs("residue", B, 1000))), dev)
     torch.manual_seed(0)
