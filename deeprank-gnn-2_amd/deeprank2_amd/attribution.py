@@ -34,14 +34,15 @@ from __future__ import annotations
 import copy
 import functools
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from deeprank2_amd import _lib, layered
-from deeprank2_amd.ensemble import _store_of
 from deeprank2_amd.fused import LDS_MAX, BatchHandle, agg_x_for, make_pass, z_lds_for
 from deeprank2_amd.neuralnets.gnn import ginet
+from deeprank2_amd.store import store_of
 
 # Whether eligible batches run dr_ginet_input_grad_pass by default (the
 # measurement behind the choice: DESIGN §5, profiles/attribution/)
@@ -50,18 +51,26 @@ FUSED_DEFAULT = True
 SCORE_KINDS = ("l2", "l1", "grad_x_input")
 
 
+class _NodeRows:
+    """What the two results share: where a requested graph's rows lie in ``dx``."""
+
+    def rows(self, i):
+        """The i-th requested graph's rows of ``dx`` (and of any per-node score), as a slice."""
+        return slice(int(self.node_off[i]), int(self.node_off[i + 1]))
+
+    def graph(self, i):
+        """The rows of the i-th requested graph, ``[N_i, F]``."""
+        return self.dx[self.rows(i)]
+
+
 @dataclass
-class InputGradients:
+class InputGradients(_NodeRows):
     dx: torch.Tensor  # [rows, F] device view: d (out . seed) / d x, the requested graphs' nodes in order
     out: torch.Tensor  # [n, out_dim] eval-mode outputs of the requested graphs
     seed: torch.Tensor  # [n, out_dim] the upstream gradient each graph was seeded with
     node_off: np.ndarray  # host int64 [n + 1]: graph i's rows are node_off[i] .. node_off[i + 1] - 1
     indices: np.ndarray  # host int64 [n]: the graphs' positions in the store
     path: str  # "fused", "layers" or "mixed"
-
-    def graph(self, i):
-        """The rows of the i-th requested graph, ``[N_i, F]``."""
-        return self.dx[int(self.node_off[i]) : int(self.node_off[i + 1])]
 
 
 def batch_rows(n_nodes, indices, batch_size):
@@ -86,10 +95,10 @@ def batch_rows(n_nodes, indices, batch_size):
     return batches, node_off
 
 
-def _check_target(model, target, seed):
-    """The refusals that need no device: the model class, and target / seed."""
+def _check_target(name, model, target, seed):
+    """The refusals of the call ``name`` that need no device: the model class, and target / seed."""
     if type(model) is not ginet.GINet:
-        msg = f"input_gradients supports GINet only (got {type(model).__name__})"
+        msg = f"{name} supports GINet only (got {type(model).__name__})"
         raise NotImplementedError(msg)
     out_dim = int(model.output_shape)
     if target is not None and seed is not None:
@@ -115,9 +124,115 @@ def _one_hot_pred(out):
     return torch.zeros_like(out).scatter_(1, out.argmax(dim=1, keepdim=True), 1.0)
 
 
-def _ig_lds(h: BatchHandle, out_dim, zs):
+def _lds(entry, h: BatchHandle, out_dim, zs):
+    """Dynamic LDS bytes of the kernel whose query is ``entry`` for the batch's largest graph (-1: no such form), asked once per handle."""
     alias, f = int(h.store.packed.transpose_aliased), h.store.n_feat
-    return int(_lib.load().dr_ginet_input_grad_lds_bytes(*h.max_sizes[:2], f, *h.max_sizes[2:], alias, out_dim, zs))
+    return h.lds((entry, out_dim, zs), lambda n, e, k0, p1, k1: getattr(_lib.load(), entry)(n, e, f, k0, p1, k1, alias, out_dim, zs))
+
+
+def _store_rows(store, gids, dev):
+    """The store rows of the nodes of graphs ``gids``, in that order (device int64)."""
+    off = np.asarray(store.packed.node_off, dtype=np.int64)
+    parts = [np.arange(off[g], off[g + 1], dtype=np.int64) for g in gids]
+    return torch.from_numpy(np.concatenate(parts) if parts else np.zeros(0, np.int64)).to(dev)
+
+
+class _Request:
+    """One call of the public function ``name``, checked and laid out: the
+    store and the weights, the requested graphs cut into batches
+    (:func:`batch_rows`), the seed, and the buffers every batch writes its part
+    of: ``buf`` (the caller's argument ``buf_name``, or a new one) and ``out``."""
+
+    def __init__(self, name, model, dataset, indices, batch_size, target, seed, fused, buf, buf_name):
+        self.model, self.target = model, target
+        self.params = [p.detach().contiguous() for p in model.ordered_params()]
+        self.dev = dev = self.params[0].device
+        if dev.type != "cuda":
+            msg = f"{name} runs on the MI355X only: move the model to a cuda device (no CPU fallback)"
+            raise RuntimeError(msg)
+        self.fused = FUSED_DEFAULT if fused is None else bool(fused)
+        self.store = store = store_of(dataset, dev)
+        self.f, self.out_dim, self.xs = store.n_feat, int(model.output_shape), store.x_stride
+        if self.f != model.input_shape:
+            msg = f"the store has {self.f} node features, model expects {model.input_shape}"
+            raise ValueError(msg)
+        self.kernel_ok = self.fused and store.dtype != "bf16"  # a bf16 store takes the layer route
+        self.idx = np.arange(store.n_graphs, dtype=np.int64) if indices is None else np.asarray(indices, dtype=np.int64).reshape(-1)
+        self.batches, self.node_off = batch_rows(store._sizes[0], self.idx, batch_size)  # noqa: SLF001
+        self.n, self.rows = n, rows = int(self.idx.size), int(self.node_off[-1])
+        if seed is not None:
+            seed_t = torch.as_tensor(seed, dtype=torch.float32, device=dev).contiguous()
+            if tuple(seed_t.shape) != (n, self.out_dim):
+                msg = f"seed must be [{n}, {self.out_dim}] (got {list(seed_t.shape)})"
+                raise ValueError(msg)
+            self.seed_t = seed_t.clone()
+        else:
+            self.seed_t = torch.zeros(n, self.out_dim, dtype=torch.float32, device=dev)
+            if target != "pred":
+                self.seed_t[:, 0 if target is None else int(target)] = 1.0
+        if buf is None:
+            buf = torch.empty((max(rows, 1), self.xs), dtype=torch.float32, device=dev)
+        elif buf.dtype != torch.float32 or buf.device != dev or buf.dim() != 2 or buf.shape[1] != self.xs or buf.shape[0] < rows or not buf.is_contiguous():  # noqa: PLR2004
+            msg = f"{buf_name} must be a contiguous fp32 [>= {rows}, {self.xs}] tensor on {dev}"
+            raise ValueError(msg)
+        self.buf, self.view = buf, buf[:rows, : self.f]  # [>= rows, x_stride], and the result's [rows, F] view of it
+        self.out = torch.empty(n, self.out_dim, dtype=torch.float32, device=dev)
+        self.w = ginet.weights_c(self.params)
+        self.bmax = max((e - s for s, e in self.batches), default=0)
+        self.taken = set()  # the routes the batches took
+
+    def handle(self, s, e):
+        return BatchHandle(self.store, self.idx[s:e].astype(np.int32))
+
+    def row_range(self, s, e):
+        """The rows of ``buf`` that the batch of requested graphs ``s .. e - 1`` owns."""
+        return int(self.node_off[s]), int(self.node_off[e])
+
+    def write_rows(self, s, e, g):
+        """A layer-route result ``g`` ``[rows of the batch, F]`` into the batch's rows, the pad columns zeroed."""
+        r0, r1 = self.row_range(s, e)
+        self.buf[r0:r1, : self.f] = g
+        self.buf[r0:r1, self.f :] = 0.0
+
+    def path(self):
+        return "mixed" if len(self.taken) > 1 else (next(iter(self.taken)) if self.taken else ("fused" if self.fused else "layers"))
+
+
+def _layer_grad(model, t, x, seed, pred=False):
+    """The layer route's kernel: ``layered.ginet_forward`` on the batch tensors
+    ``t`` at ``t.x = x``, and ``torch.autograd.grad``: the detached outputs and
+    ``d (out . seed) / d x``.  ``pred`` first makes ``seed`` (the caller's view) that forward's one-hot arg-max."""
+    t.x = x.requires_grad_(True)
+    with torch.enable_grad():
+        o = layered.ginet_forward(model, t, training=False)
+        if pred:
+            seed[:] = _one_hot_pred(o.detach())
+        (g,) = torch.autograd.grad((o * seed).sum(), t.x)
+    return o.detach(), g
+
+
+def _input_grad_fused(rq: _Request, c, h: BatchHandle, s, e, z, zs):
+    """One ``dr_ginet_input_grad_pass`` launch: the batch's rows of ``dx`` in place."""
+    out_dim, dev = rq.out_dim, rq.dev
+    if c.slab is None:
+        c.slab = torch.empty(rq.bmax * ginet.slab_stride(rq.f), dtype=torch.float32, device=dev)
+        c.head = torch.zeros(rq.bmax * ginet.head_stride(out_dim), dtype=torch.float32, device=dev)
+    if rq.target == "pred":  # one forward through the eval path, then the one-hot on the device
+        ginet.graph_pass(h, rq.params, out_dim, _lib.DR_PASS_FORWARD, out=rq.out[s:e])
+        rq.seed_t[s:e] = _one_hot_pred(rq.out[s:e])
+    p = make_pass(out_dim, _lib.DR_PASS_FORWARD | _lib.DR_PASS_BACKWARD, dout=rq.seed_t[s:e], out=rq.out[s:e], slab=c.slab, head=c.head)
+    ig = _lib.InputGradC()
+    ig.dx, ig.row_off, ig.dx_stride = rq.buf.data_ptr(), c.row_off.data_ptr() + 8 * s, rq.xs
+    lds = _lds("dr_ginet_input_grad_lds_bytes", h, out_dim, zs)
+    rc = _lib.load().dr_ginet_input_grad_pass(rq.store.cstruct(), h.descs.data_ptr(), h.B, rq.w, p, ig, _lib.ptr(z), zs, lds, _lib.stream_ptr(dev))
+    _lib.check(rc, "dr_ginet_input_grad_pass")
+
+
+def _input_grad_layers(rq: _Request, h: BatchHandle, s, e):
+    """The batch through ``layered.ginet_forward`` and ``torch.autograd.grad``."""
+    t = copy.copy(layered.batch_tensors(h))
+    rq.out[s:e], g = _layer_grad(rq.model, t, t.x.detach().clone(), rq.seed_t[s:e], pred=rq.target == "pred")
+    rq.write_rows(s, e, g)
 
 
 def input_gradients(model, dataset, indices=None, batch_size=64, target=None, seed=None, fused=None, *, dx_out=None) -> InputGradients:
@@ -140,79 +255,21 @@ def input_gradients(model, dataset, indices=None, batch_size=64, target=None, se
     slab and head of the training pass are allocated once.  The gradient with
     respect to ``edge_attr`` is exactly zero (module docstring) and is not
     returned."""
-    _check_target(model, target, seed)
-    params = [p.detach().contiguous() for p in model.ordered_params()]
-    dev = params[0].device
-    if dev.type != "cuda":
-        msg = "input_gradients runs on the MI355X only: move the model to a cuda device (no CPU fallback)"
-        raise RuntimeError(msg)
-    fused = FUSED_DEFAULT if fused is None else bool(fused)
-    store = _store_of(dataset, dev)
-    f, out_dim, xs = store.n_feat, int(model.output_shape), store.x_stride
-    if f != model.input_shape:
-        msg = f"the store has {f} node features, model expects {model.input_shape}"
-        raise ValueError(msg)
-    idx = np.arange(store.n_graphs, dtype=np.int64) if indices is None else np.asarray(indices, dtype=np.int64).reshape(-1)
-    batches, node_off = batch_rows(store._sizes[0], idx, batch_size)  # noqa: SLF001
-    n, rows = int(idx.size), int(node_off[-1])
-
-    if seed is not None:
-        seed_t = torch.as_tensor(seed, dtype=torch.float32, device=dev).contiguous()
-        if tuple(seed_t.shape) != (n, out_dim):
-            msg = f"seed must be [{n}, {out_dim}] (got {list(seed_t.shape)})"
-            raise ValueError(msg)
-        seed_t = seed_t.clone()
-    else:
-        seed_t = torch.zeros(n, out_dim, dtype=torch.float32, device=dev)
-        if target != "pred":
-            seed_t[:, 0 if target is None else int(target)] = 1.0
-
-    if dx_out is None:
-        dx_buf = torch.empty((max(rows, 1), xs), dtype=torch.float32, device=dev)
-    else:
-        dx_buf = dx_out
-        if dx_buf.dtype != torch.float32 or dx_buf.device != dev or dx_buf.dim() != 2 or dx_buf.shape[1] != xs or dx_buf.shape[0] < rows or not dx_buf.is_contiguous():  # noqa: PLR2004
-            msg = f"dx_out must be a contiguous fp32 [>= {rows}, {xs}] tensor on {dev}"
-            raise ValueError(msg)
-    out = torch.empty(n, out_dim, dtype=torch.float32, device=dev)
-    row_off = torch.from_numpy(node_off[:-1].copy()).to(dev) if n else None
-    w = ginet.weights_c(params)
-    bmax = max((e - s for s, e in batches), default=0)
-    slab = head = None  # the training pass's partials: scratch here, made on the first fused batch
-    lib = _lib.load()
-    taken = set()
-    for s, e in batches:
-        h = BatchHandle(store, idx[s:e].astype(np.int32))
-        z = agg_x_for(ginet.SPEC, h) if fused and store.dtype != "bf16" else None
-        zs = store.agg_x_stride if z is not None else 0
-        if fused and store.dtype != "bf16" and not h.nonfinite and _ig_lds(h, out_dim, zs) <= LDS_MAX:
-            if slab is None:
-                slab = torch.empty(bmax * ginet.slab_stride(f), dtype=torch.float32, device=dev)
-                head = torch.zeros(bmax * ginet.head_stride(out_dim), dtype=torch.float32, device=dev)
-            if target == "pred":  # one forward through the eval path, then the one-hot on the device
-                ginet.graph_pass(h, params, out_dim, _lib.DR_PASS_FORWARD, out=out[s:e])
-                seed_t[s:e] = _one_hot_pred(out[s:e])
-            p = make_pass(out_dim, _lib.DR_PASS_FORWARD | _lib.DR_PASS_BACKWARD, dout=seed_t[s:e], out=out[s:e], slab=slab, head=head)
-            ig = _lib.InputGradC()
-            ig.dx, ig.row_off, ig.dx_stride = dx_buf.data_ptr(), row_off.data_ptr() + 8 * s, xs
-            rc = lib.dr_ginet_input_grad_pass(store.cstruct(), h.descs.data_ptr(), h.B, w, p, ig, _lib.ptr(z), zs, _ig_lds(h, out_dim, zs), _lib.stream_ptr(dev))
-            _lib.check(rc, "dr_ginet_input_grad_pass")
-            taken.add("fused")
+    _check_target("input_gradients", model, target, seed)
+    rq = _Request("input_gradients", model, dataset, indices, batch_size, target, seed, fused, dx_out, "dx_out")
+    # each graph's first row of dx; the fused route's slab and head (the training pass's partials: scratch here), made on its first batch
+    c = SimpleNamespace(row_off=torch.from_numpy(rq.node_off[:-1].copy()).to(rq.dev) if rq.n else None, slab=None, head=None)
+    for s, e in rq.batches:
+        h = rq.handle(s, e)
+        z = agg_x_for(ginet.SPEC, h) if rq.kernel_ok else None  # (the Z array off: the kernel's gather form, z null and zs 0)
+        zs = rq.store.agg_x_stride if z is not None else 0
+        if rq.kernel_ok and not h.nonfinite and _lds("dr_ginet_input_grad_lds_bytes", h, rq.out_dim, zs) <= LDS_MAX:
+            _input_grad_fused(rq, c, h, s, e, z, zs)
+            rq.taken.add("fused")
         else:
-            t = copy.copy(layered.batch_tensors(h))
-            t.x = t.x.detach().clone().requires_grad_(True)
-            with torch.enable_grad():
-                o = layered.ginet_forward(model, t, training=False)
-                if target == "pred":
-                    seed_t[s:e] = _one_hot_pred(o.detach())
-                (g,) = torch.autograd.grad((o * seed_t[s:e]).sum(), t.x)
-            out[s:e] = o.detach()
-            r0, r1 = int(node_off[s]), int(node_off[e])
-            dx_buf[r0:r1, :f] = g
-            dx_buf[r0:r1, f:] = 0.0
-            taken.add("layers")
-    path = "mixed" if len(taken) > 1 else (taken.pop() if taken else ("fused" if fused else "layers"))
-    return InputGradients(dx_buf[:rows, :f], out, seed_t, node_off, idx, path)
+            _input_grad_layers(rq, h, s, e)
+            rq.taken.add("layers")
+    return InputGradients(rq.view, rq.out, rq.seed_t, rq.node_off, rq.idx, rq.path())
 
 
 # ---------------------------------------------------------------------------
@@ -253,7 +310,7 @@ def _quadrature_cached(method, steps):
 
 
 @dataclass
-class IntegratedGradients:
+class IntegratedGradients(_NodeRows):
     attr: torch.Tensor  # [rows, F] device view: (x - baseline) * sum_s w_s g_s, the requested graphs' nodes in order
     out: torch.Tensor  # [n, out_dim] eval-mode outputs at x
     out_baseline: torch.Tensor  # [n, out_dim] eval-mode outputs at the baseline
@@ -274,22 +331,6 @@ class IntegratedGradients:
     def node_attr(self):
         """The signed attribution of each node, ``[rows]``: its features' sum."""
         return self.attr.sum(dim=1)
-
-    def graph(self, i):
-        """The rows of the i-th requested graph, ``[N_i, F]``."""
-        return self.attr[int(self.node_off[i]) : int(self.node_off[i + 1])]
-
-
-def _store_rows(store, gids):
-    """Host int64: the store rows of the nodes of graphs ``gids``, in that order."""
-    off = np.asarray(store.packed.node_off, dtype=np.int64)
-    parts = [np.arange(off[g], off[g + 1], dtype=np.int64) for g in gids]
-    return np.concatenate(parts) if parts else np.zeros(0, np.int64)
-
-
-def _intgrad_lds(h: BatchHandle, out_dim, zs):
-    alias, f = int(h.store.packed.transpose_aliased), h.store.n_feat
-    return int(_lib.load().dr_ginet_integrated_grad_lds_bytes(*h.max_sizes[:2], f, *h.max_sizes[2:], alias, out_dim, zs))
 
 
 def _forward_z(h: BatchHandle, w, out_dim, z, zs, out):
@@ -324,6 +365,59 @@ def _check_ig_args(model, steps, method, groups, baseline, quad):
     return alpha.astype(np.float32), weight.astype(np.float32), int(groups)
 
 
+def _integrated_fused(rq: _Request, c, h: BatchHandle, s, e):
+    """The Z-input forward at ``x``, the same at the baseline, and one
+    ``dr_ginet_integrated_grad_pass``: the batch's rows of ``attr`` in place."""
+    f, out_dim, dev, n_groups, zs = rq.f, rq.out_dim, rq.dev, c.n_groups, c.zs
+    if c.slab is None:  # per-group slab / head / out of the training pass and the partial rows: scratch, made on the first fused batch
+        c.slab = torch.empty(n_groups * rq.bmax * ginet.slab_stride(f), dtype=torch.float32, device=dev)
+        c.head = torch.zeros(n_groups * rq.bmax * ginet.head_stride(out_dim), dtype=torch.float32, device=dev)
+        c.outs = torch.empty(n_groups * rq.bmax * out_dim, dtype=torch.float32, device=dev)
+        c.part = torch.empty((n_groups, max(c.rmax, 1), rq.xs), dtype=torch.float32, device=dev)
+    _forward_z(h, rq.w, out_dim, c.z_all, zs, rq.out[s:e])
+    if c.zb is not None:
+        _forward_z(h, rq.w, out_dim, c.zb, zs, c.out_b[s:e])
+    else:
+        if c.out_b0 is None:  # a zero baseline's outputs: Z = 0 pools to zero features, so the head on a zero vector
+            c.out_b0 = torch.relu(rq.params[13]) @ rq.params[14].t() + rq.params[15]
+        c.out_b[s:e] = c.out_b0
+    if rq.target == "pred":
+        rq.seed_t[s:e] = _one_hot_pred(rq.out[s:e])
+    p = make_pass(out_dim, _lib.DR_PASS_FORWARD | _lib.DR_PASS_BACKWARD, dout=rq.seed_t[s:e])
+    ig = _lib.IntegratedGradC()
+    ig.attr, ig.row_off, ig.dx_stride = rq.buf.data_ptr(), c.offs.data_ptr() + 8 * s, rq.xs
+    ig.n_steps, ig.n_groups = c.n_steps, n_groups
+    ig.alpha, ig.weight = c.quad_t.data_ptr(), c.quad_t.data_ptr() + 4 * c.n_steps
+    ig.zb, ig.xb = _lib.ptr(c.zb), _lib.ptr(c.xb) if c.zb is not None else None
+    ig.part, ig.part_off, ig.part_rows = c.part.data_ptr(), c.offs.data_ptr() + 8 * (rq.n + s), c.part.shape[1]
+    ig.attr_sum = c.attr_sum.data_ptr() + 8 * s
+    ig.slab, ig.head, ig.out = c.slab.data_ptr(), c.head.data_ptr(), c.outs.data_ptr()
+    lds = _lds("dr_ginet_integrated_grad_lds_bytes", h, out_dim, zs)
+    rc = _lib.load().dr_ginet_integrated_grad_pass(rq.store.cstruct(), h.descs.data_ptr(), h.B, rq.w, p, ig, c.z_all.data_ptr(), zs, lds, _lib.stream_ptr(dev))
+    _lib.check(rc, "dr_ginet_integrated_grad_pass")
+
+
+def _integrated_layers(rq: _Request, c, h: BatchHandle, s, e):
+    """The batch step by step: :func:`_layer_grad` at every quadrature node."""
+    t = copy.copy(layered.batch_tensors(h))
+    x0 = t.x.detach()
+    b0 = torch.zeros_like(x0) if c.xb is None else c.xb[_store_rows(rq.store, rq.idx[s:e], rq.dev), : rq.f]
+    with torch.no_grad():
+        o = layered.ginet_forward(rq.model, t, training=False)
+        t.x = b0
+        c.out_b[s:e] = layered.ginet_forward(rq.model, t, training=False)
+    rq.out[s:e] = o
+    if rq.target == "pred":
+        rq.seed_t[s:e] = _one_hot_pred(o)
+    acc = torch.zeros_like(x0)
+    for k in range(c.n_steps):
+        _, g = _layer_grad(rq.model, t, b0 + float(c.alpha[k]) * (x0 - b0), rq.seed_t[s:e])
+        acc += float(c.weight[k]) * g
+    a = (x0 - b0) * acc
+    rq.write_rows(s, e, a)
+    c.attr_sum[s:e] = torch.zeros(e - s, dtype=torch.float64, device=rq.dev).index_add_(0, t.batch.long(), a.double().sum(dim=1))
+
+
 def integrated_gradients(model, dataset, indices=None, batch_size=64, target=None, seed=None, baseline=None, steps=32, method="gausslegendre", groups=None, fused=None, *, attr_out=None, _quadrature=None) -> IntegratedGradients:
     """Integrated gradients (Sundararajan et al. 2017) of ``out . seed`` with
     respect to the node features, for the graphs ``indices`` of ``dataset``:
@@ -352,152 +446,51 @@ def integrated_gradients(model, dataset, indices=None, batch_size=64, target=Non
     ``layered.ginet_forward`` + ``torch.autograd.grad`` with the same nodes and
     weights.  The ``edge_attr`` attribution is exactly zero (module docstring)
     and is not returned."""
-    _check_target(model, target, seed)
+    _check_target("integrated_gradients", model, target, seed)
     alpha, weight, n_groups = _check_ig_args(model, steps, method, groups, baseline, _quadrature)
-    n_steps = int(alpha.size)
-    params = [p.detach().contiguous() for p in model.ordered_params()]
-    dev = params[0].device
-    if dev.type != "cuda":
-        msg = "integrated_gradients runs on the MI355X only: move the model to a cuda device (no CPU fallback)"
-        raise RuntimeError(msg)
-    fused = FUSED_DEFAULT if fused is None else bool(fused)
-    store = _store_of(dataset, dev)
-    f, out_dim, xs = store.n_feat, int(model.output_shape), store.x_stride
-    if f != model.input_shape:
-        msg = f"the store has {f} node features, model expects {model.input_shape}"
-        raise ValueError(msg)
-    idx = np.arange(store.n_graphs, dtype=np.int64) if indices is None else np.asarray(indices, dtype=np.int64).reshape(-1)
-    batches, node_off = batch_rows(store._sizes[0], idx, batch_size)  # noqa: SLF001
-    n, rows = int(idx.size), int(node_off[-1])
-
-    if seed is not None:
-        seed_t = torch.as_tensor(seed, dtype=torch.float32, device=dev).contiguous()
-        if tuple(seed_t.shape) != (n, out_dim):
-            msg = f"seed must be [{n}, {out_dim}] (got {list(seed_t.shape)})"
-            raise ValueError(msg)
-        seed_t = seed_t.clone()
-    else:
-        seed_t = torch.zeros(n, out_dim, dtype=torch.float32, device=dev)
-        if target != "pred":
-            seed_t[:, 0 if target is None else int(target)] = 1.0
-
-    if attr_out is None:
-        attr_buf = torch.empty((max(rows, 1), xs), dtype=torch.float32, device=dev)
-    else:
-        attr_buf = attr_out
-        if attr_buf.dtype != torch.float32 or attr_buf.device != dev or attr_buf.dim() != 2 or attr_buf.shape[1] != xs or attr_buf.shape[0] < rows or not attr_buf.is_contiguous():  # noqa: PLR2004
-            msg = f"attr_out must be a contiguous fp32 [>= {rows}, {xs}] tensor on {dev}"
-            raise ValueError(msg)
-
-    lib = _lib.load()
-    stream = _lib.stream_ptr(dev)
-    z_all = store.agg_x() if fused and store.dtype != "bf16" else None
-    zs = store.agg_x_stride
-    # the baseline in x's layout and its neighbour sums in Z's, once per call
-    xb = zb = None
+    rq = _Request("integrated_gradients", model, dataset, indices, batch_size, target, seed, fused, attr_out, "attr_out")
+    # once per call: the baseline in x's layout (xb) and its neighbour sums in Z's (zb), the buffers beside the request's, the offsets and the quadrature on the device
+    store, dev, f, n, node_off, batches = rq.store, rq.dev, rq.f, rq.n, rq.node_off, rq.batches
+    c = SimpleNamespace(alpha=alpha, weight=weight, n_steps=int(alpha.size), n_groups=n_groups, xb=None, zb=None, out_b0=None, slab=None)
+    c.z_all = store.agg_x() if rq.kernel_ok else None  # None: there is no gather form, every batch takes the layer route
+    c.zs = store.agg_x_stride
     if baseline is not None:
         b_t = torch.as_tensor(baseline, dtype=torch.float32, device=dev)
-        xb = torch.zeros((max(1, int(store.x.shape[0])), xs), dtype=torch.float32, device=dev)
+        c.xb = xb = torch.zeros((max(1, int(store.x.shape[0])), rq.xs), dtype=torch.float32, device=dev)
         if b_t.dim() == 1:
             xb[:, :f] = b_t
         else:
-            if b_t.shape[0] != rows:
-                msg = f"baseline must be [{f}] or [{rows}, {f}] (got {list(b_t.shape)})"
+            if b_t.shape[0] != rq.rows:
+                msg = f"baseline must be [{f}] or [{rq.rows}, {f}] (got {list(b_t.shape)})"
                 raise ValueError(msg)
-            if np.unique(idx).size != idx.size:
+            if np.unique(rq.idx).size != rq.idx.size:
                 msg = "a per-node baseline needs every requested graph named once"
                 raise ValueError(msg)
-            xb[torch.from_numpy(_store_rows(store, idx)).to(dev), :f] = b_t
-        if z_all is not None:
-            zb = torch.empty_like(z_all)
+            xb[_store_rows(store, rq.idx, dev), :f] = b_t
+        if c.z_all is not None:
+            c.zb = torch.empty_like(c.z_all)
             st = _lib.GraphStoreC.from_buffer_copy(store.cstruct())
             st.x = xb.data_ptr()
-            _lib.check(lib.dr_aggregate_x(st, zb.data_ptr(), zs, 0, store.n_graphs, stream), "dr_aggregate_x")
-
-    out = torch.empty(n, out_dim, dtype=torch.float32, device=dev)
-    out_b = torch.empty(n, out_dim, dtype=torch.float32, device=dev)
-    attr_sum = torch.zeros(n, dtype=torch.float64, device=dev)
-    w = ginet.weights_c(params)
-    bmax = max((e - s for s, e in batches), default=0)
-    rmax = max((int(node_off[e] - node_off[s]) for s, e in batches), default=0)
-    offs = None  # [2, n]: each graph's first row of attr, and its first row inside its batch (the partial rows)
+            _lib.check(_lib.load().dr_aggregate_x(st, c.zb.data_ptr(), c.zs, 0, store.n_graphs, _lib.stream_ptr(dev)), "dr_aggregate_x")
+    c.out_b = torch.empty(n, rq.out_dim, dtype=torch.float32, device=dev)
+    c.attr_sum = torch.zeros(n, dtype=torch.float64, device=dev)
+    c.rmax = max((int(node_off[e] - node_off[s]) for s, e in batches), default=0)
+    c.offs = None  # [2, n]: each graph's first row of attr, and its first row inside its batch (the partial rows)
     if n:
         first = np.repeat(node_off[[s for s, _ in batches]], [e - s for s, e in batches])
-        offs = torch.from_numpy(np.stack([node_off[:-1], node_off[:-1] - first])).to(dev)
-    quad_t = torch.from_numpy(np.stack([alpha, weight])).to(dev)  # [2, S]
-    out_b0 = None  # a zero baseline's outputs: Z = 0 pools to zero features, so the head on a zero vector
-    scratch = None  # per-group slab / head / out of the training pass and the partial rows, made on the first fused batch
-    taken = set()
+        c.offs = torch.from_numpy(np.stack([node_off[:-1], node_off[:-1] - first])).to(dev)
+    c.quad_t = torch.from_numpy(np.stack([alpha, weight])).to(dev)  # [2, S]
     for s, e in batches:
-        h = BatchHandle(store, idx[s:e].astype(np.int32))
-        lds = _intgrad_lds(h, out_dim, zs) if z_all is not None else -1
-        if z_all is not None and not h.nonfinite and 0 <= lds <= LDS_MAX:
-            if scratch is None:
-                scratch = (
-                    torch.empty(n_groups * bmax * ginet.slab_stride(f), dtype=torch.float32, device=dev),
-                    torch.zeros(n_groups * bmax * ginet.head_stride(out_dim), dtype=torch.float32, device=dev),
-                    torch.empty(n_groups * bmax * out_dim, dtype=torch.float32, device=dev),
-                    torch.empty((n_groups, max(rmax, 1), xs), dtype=torch.float32, device=dev),
-                )
-            _forward_z(h, w, out_dim, z_all, zs, out[s:e])
-            if zb is not None:
-                _forward_z(h, w, out_dim, zb, zs, out_b[s:e])
-            else:
-                if out_b0 is None:
-                    out_b0 = torch.relu(params[13]) @ params[14].t() + params[15]
-                out_b[s:e] = out_b0
-            if target == "pred":
-                seed_t[s:e] = _one_hot_pred(out[s:e])
-            p = make_pass(out_dim, _lib.DR_PASS_FORWARD | _lib.DR_PASS_BACKWARD, dout=seed_t[s:e])
-            ig = _lib.IntegratedGradC()
-            ig.attr, ig.row_off, ig.dx_stride = attr_buf.data_ptr(), offs.data_ptr() + 8 * s, xs
-            ig.n_steps, ig.n_groups = n_steps, n_groups
-            ig.alpha, ig.weight = quad_t.data_ptr(), quad_t.data_ptr() + 4 * n_steps
-            ig.zb, ig.xb = _lib.ptr(zb), _lib.ptr(xb) if zb is not None else None
-            ig.part, ig.part_off, ig.part_rows = scratch[3].data_ptr(), offs.data_ptr() + 8 * (n + s), scratch[3].shape[1]
-            ig.attr_sum = attr_sum.data_ptr() + 8 * s
-            ig.slab, ig.head, ig.out = scratch[0].data_ptr(), scratch[1].data_ptr(), scratch[2].data_ptr()
-            rc = lib.dr_ginet_integrated_grad_pass(store.cstruct(), h.descs.data_ptr(), h.B, w, p, ig, z_all.data_ptr(), zs, lds, stream)
-            _lib.check(rc, "dr_ginet_integrated_grad_pass")
-            taken.add("fused")
+        h = rq.handle(s, e)
+        lds = _lds("dr_ginet_integrated_grad_lds_bytes", h, rq.out_dim, c.zs) if c.z_all is not None else -1
+        if c.z_all is not None and not h.nonfinite and 0 <= lds <= LDS_MAX:
+            _integrated_fused(rq, c, h, s, e)
+            rq.taken.add("fused")
         else:
-            t = copy.copy(layered.batch_tensors(h))
-            x0 = t.x.detach()
-            if xb is None:
-                b0 = torch.zeros_like(x0)
-            else:
-                b0 = xb[torch.from_numpy(_store_rows(store, idx[s:e])).to(dev), :f]
-            with torch.no_grad():
-                o = layered.ginet_forward(model, t, training=False)
-                t.x = b0
-                out_b[s:e] = layered.ginet_forward(model, t, training=False)
-            out[s:e] = o
-            if target == "pred":
-                seed_t[s:e] = _one_hot_pred(o)
-            acc = torch.zeros_like(x0)
-            for k in range(n_steps):
-                t.x = (b0 + float(alpha[k]) * (x0 - b0)).requires_grad_(True)
-                with torch.enable_grad():
-                    ok = layered.ginet_forward(model, t, training=False)
-                    (g,) = torch.autograd.grad((ok * seed_t[s:e]).sum(), t.x)
-                acc += float(weight[k]) * g
-            a = (x0 - b0) * acc
-            r0, r1 = int(node_off[s]), int(node_off[e])
-            attr_buf[r0:r1, :f] = a
-            attr_buf[r0:r1, f:] = 0.0
-            attr_sum[s:e] = torch.zeros(e - s, dtype=torch.float64, device=dev).index_add_(0, t.batch.long(), a.double().sum(dim=1))
-            taken.add("layers")
-    path = "mixed" if len(taken) > 1 else (taken.pop() if taken else ("fused" if fused else "layers"))
-    delta = attr_sum - ((out.double() - out_b.double()) * seed_t.double()).sum(dim=1)
-    return IntegratedGradients(attr_buf[:rows, :f], out, out_b, seed_t, attr_sum, delta, node_off, idx, path, alpha, weight)
-
-
-def _rows_of(result: InputGradients, store):
-    """The store rows of the result's nodes, in the result's order (device int64)."""
-    off = np.asarray(store.packed.node_off, dtype=np.int64)
-    parts = [np.arange(off[g], off[g + 1], dtype=np.int64) for g in result.indices]
-    rows = np.concatenate(parts) if parts else np.zeros(0, np.int64)
-    return torch.from_numpy(rows).to(result.dx.device)
+            _integrated_layers(rq, c, h, s, e)
+            rq.taken.add("layers")
+    delta = c.attr_sum - ((rq.out.double() - c.out_b.double()) * rq.seed_t.double()).sum(dim=1)
+    return IntegratedGradients(rq.view, rq.out, c.out_b, rq.seed_t, c.attr_sum, delta, rq.node_off, rq.idx, rq.path(), alpha, weight)
 
 
 def node_scores(result: InputGradients, store_or_dataset, kind="l2"):
@@ -512,13 +505,13 @@ def node_scores(result: InputGradients, store_or_dataset, kind="l2"):
         return dx.square().sum(dim=1).sqrt()
     if kind == "l1":
         return dx.abs().sum(dim=1)
-    store = _store_of(store_or_dataset, dx.device)
-    x = store.x[_rows_of(result, store), : dx.shape[1]]
+    store = store_of(store_or_dataset, dx.device)
+    x = store.x[_store_rows(store, result.indices, dx.device), : dx.shape[1]]
     return (x * dx).sum(dim=1)
 
 
 def top_nodes(result: InputGradients, scores, i, k):
     """Host indices (local node ids, int64) of the ``k`` highest-scoring nodes
     of the i-th requested graph, highest first; equal scores in node order."""
-    s = scores[int(result.node_off[i]) : int(result.node_off[i + 1])].detach().cpu().numpy()
+    s = scores[result.rows(i)].detach().cpu().numpy()
     return np.argsort(-s, kind="stable")[: max(0, int(k))].astype(np.int64)

@@ -54,7 +54,7 @@ from deeprank2_amd.engine import LOSS_KINDS, OPT_KINDS, FusedTrainStep
 from deeprank2_amd.epoch import StagedBatches, store_fits
 from deeprank2_amd.fused import LDS_MAX, BatchHandle, agg_x_for, capture_after_warmup, launch, lds_for, make_pass, slab_rows_for, z_lds_for
 from deeprank2_amd.neuralnets.gnn.ginet import GINet
-from deeprank2_amd.store import GraphStore, pack_graphs
+from deeprank2_amd.store import store_of
 
 MAX_MEMBERS = _lib.DR_MAX_MEMBERS
 
@@ -282,14 +282,6 @@ class EnsembleResult:
     best_epoch: np.ndarray | None = None  # [K] int: the epoch of each member's lowest validation loss (-1: none; None without val_indices)
     stopped_epoch: np.ndarray | None = None  # [K] int: the epoch after which patience stopped the member (-1: never)
     step: FusedEnsembleStep | None = None  # the step that trained them: ``step.steps[k]`` holds member k's optimizer state and device counters
-
-
-def _store_of(dataset, device):
-    if isinstance(dataset, GraphStore):
-        return dataset
-    if callable(getattr(dataset, "graph_store", None)):
-        return dataset.graph_store(device)
-    return GraphStore(pack_graphs(list(dataset)), device)
 
 
 class _Handle:
@@ -860,7 +852,7 @@ def predict_ensemble(models, dataset, indices=None, batch_size=64, task=None):
     if task not in ENS_KINDS:
         msg = f"task must be one of {sorted(ENS_KINDS)} (got {task!r})"
         raise ValueError(msg)
-    store = _store_of(dataset, _device_of(models))
+    store = store_of(dataset, _device_of(models))
     idx = np.arange(store.n_graphs, dtype=np.int64) if indices is None else np.asarray(indices, dtype=np.int64).reshape(-1)
     batches = epoch_batches(idx, batch_size, False, 0, 0, 0)
     runner = _runner_for(models, store, [[len(b) for b in batches]] * len(models))
@@ -888,7 +880,7 @@ def score_ensemble(models, dataset, indices=None, batch_size=64, loss="mse", los
         msg = f"task {task!r} does not go with loss {loss!r}: 'classif' scores the cross entropy, 'regress' the other losses"
         raise ValueError(msg)
     models = _check_members(models, "an ensemble score")
-    store = _store_of(dataset, _device_of(models))
+    store = store_of(dataset, _device_of(models))
     pred = predict_ensemble(models, store, indices, batch_size, task)
     with torch.cuda.device(store.device):
         gids = torch.from_numpy(pred.indices).to(store.device)
@@ -988,7 +980,7 @@ def out_of_fold_predictions(models, dataset, val_indices, batch_size=64):
     ``FusedEnsembleForward``."""
     models = _check_members(models, "an out-of-fold prediction")
     val = _disjoint(val_indices, len(models))
-    store = _store_of(dataset, _device_of(models))
+    store = store_of(dataset, _device_of(models))
     dev = store.device
     batches = [epoch_batches(v, batch_size, False, 0, 0, 0) for v in val]
     runner = FusedEnsembleForward(models, store, [[len(b) for b in bs] for bs in batches])
@@ -1050,7 +1042,7 @@ def train_ensemble(models, dataset, member_indices=None, nepoch=1, batch_size=32
     stopping = MemberStopping(k, patience, min_delta) if val_indices is not None else None
     step_kw.setdefault("max_batch", batch_size)
     ens = FusedEnsembleStep(models, **step_kw)
-    store = _store_of(dataset, ens.device)
+    store = store_of(dataset, ens.device)
     if member_indices is None:
         member_indices = [np.arange(store.n_graphs)] * k
     if len(member_indices) != k or (val_indices is not None and len(val_indices) != k):

@@ -547,3 +547,13 @@ class GraphStore:
     def edges_in(self, gids_host):
         n, e, *_ = self._sizes
         return int(e[np.asarray(gids_host, dtype=np.int64)].sum())
+
+
+def store_of(dataset, device):
+    """The resident store of ``dataset``: a ``GraphStore`` as it is, a
+    ``GraphDataset``'s own (``graph_store``), or one packed from its records."""
+    if isinstance(dataset, GraphStore):
+        return dataset
+    if callable(getattr(dataset, "graph_store", None)):
+        return dataset.graph_store(device)
+    return GraphStore(pack_graphs(list(dataset)), device)

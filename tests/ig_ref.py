@@ -1,5 +1,6 @@
-"""TEST INFRASTRUCTURE: the CPU reference of GINet integrated gradients, and
-the named batches, baselines and targets the host and GPU tests share.
+"""TEST INFRASTRUCTURE: the CPU reference of GINet integrated gradients and
+the baselines the host and GPU tests share (the named batches, models and
+targets are ``attribution_ref``'s).
 
 The reference is the oracle model (``oracle/gnn_ref.GINet``) in eval mode, run
 in float64 (``torch.set_default_dtype`` around the calls, as
@@ -26,55 +27,12 @@ import numpy as np
 import torch
 
 import attribution_ref
-import graph_zoo
+from attribution_ref import BATCHES, datas, n_feat, oracle_model, target_of  # noqa: F401 (the tests read them here too)
 from deeprank2_amd import attribution
-from deeprank2_amd.utils.synthetic import make_dataset
-from oracle import data_ref, gnn_ref
 
 TOL = dict(rtol=1e-4, atol=1e-4)
-BATCHES = ("asym", "deg", "f33", "f12")
 BASELINES = ("zero", "mean")
-# target name -> (out_dim, target)
-TARGETS = {"one": (1, None), "t1": (2, 1), "pred": (2, "pred"), "seed": (2, "seed")}
-
-
-def _synthetic(n_feat, seed):
-    """``test_gpu_attribution._synthetic``: four synthetic graphs with seeded
-    normal features (no ties between the members of a cluster)."""
-    graphs = make_dataset(4, seed=seed, n_lo=20, n_hi=90, mean_degree=6.0, k_lo=2, k_hi=14, n_feat=n_feat)
-    rng = np.random.default_rng(seed)
-    for g in graphs:
-        g["x"] = rng.normal(size=g["x"].shape).astype(np.float32)
-    return tuple(data_ref.synthetic_to_data(g, f"f{n_feat}_{j}") for j, g in enumerate(graphs))
-
-
-@functools.lru_cache(maxsize=None)
-def datas(batch):
-    if batch == "asym":
-        return tuple(graph_zoo.asymmetric(**graph_zoo.ASYM_BATCH))
-    if batch == "deg":
-        return tuple(graph_zoo.degenerate())
-    if batch == "f33":
-        return _synthetic(33, 71)
-    assert batch == "f12"
-    return _synthetic(12, 72)
-
-
-def n_feat(batch):
-    return {"f33": 33, "f12": 12}.get(batch, 30)
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_model(nf, out_dim):
-    torch.manual_seed(11)
-    return gnn_ref.GINet(nf, out_dim, 3).eval()
-
-
-def target_of(batch, name):
-    out_dim, target = TARGETS[name]
-    if target == "seed":
-        target = torch.randn(len(datas(batch)), out_dim, generator=torch.Generator().manual_seed(5))
-    return out_dim, target
+TARGETS = ("one", "t1", "pred", "seed")  # the names of ``attribution_ref.TARGETS`` these tests run
 
 
 @functools.lru_cache(maxsize=None)

@@ -23,90 +23,36 @@ from _util import assert_grad_close
 
 import attribution_ref
 import graph_zoo
+from attribution_ref import DEV
+from attribution_ref import model as _model
+from attribution_ref import store as _store
 from deeprank2_amd import _lib, attribution
 from deeprank2_amd.fused import LDS_MAX, BatchHandle
-from deeprank2_amd.neuralnets.gnn.ginet import GINet
 from deeprank2_amd.store import GraphStore, pack_graphs, records_from_batch
 from deeprank2_amd.utils.synthetic import make_dataset
-from oracle import data_ref, gnn_ref
+from oracle import data_ref
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 TOL = dict(rtol=1e-4, atol=1e-4)
-
-# target name -> (out_dim, target): every case the fused pass takes at F = 30
-TARGETS = {"one": (1, None), "t0": (2, 0), "t1": (2, 1), "pred": (2, "pred"), "seed": (2, "seed")}
-
-
-def _synthetic(n_feat, seed):
-    """Four synthetic graphs with ``n_feat`` continuous features.  (The
-    generator's first 24 columns are one-hot residue classes: at F = 12 a
-    graph has a dozen distinct x rows, members of one cluster then have
-    bit-equal neighbour sums, and which of two tied members the depth-0 max
-    pool routes the gradient to is decided by rounding — aggregate-then-GEMM
-    here, GEMM-then-scatter in the oracle — so dx is not unique there, while
-    every parameter gradient is.  Seeded normal features have no ties.)"""
-    graphs = make_dataset(4, seed=seed, n_lo=20, n_hi=90, mean_degree=6.0, k_lo=2, k_hi=14, n_feat=n_feat)
-    rng = np.random.default_rng(seed)
-    for g in graphs:
-        g["x"] = rng.normal(size=g["x"].shape).astype(np.float32)
-    return tuple(data_ref.synthetic_to_data(g, f"f{n_feat}_{j}") for j, g in enumerate(graphs))
-
-
-@functools.lru_cache(maxsize=None)
-def _datas(batch):
-    if batch == "asym":
-        return tuple(graph_zoo.asymmetric(**graph_zoo.ASYM_BATCH))
-    if batch == "deg":
-        return tuple(graph_zoo.degenerate())
-    if batch == "f33":
-        return _synthetic(33, 71)
-    assert batch == "f12"
-    return _synthetic(12, 72)
-
-
-def _n_feat(batch):
-    return {"f33": 33, "f12": 12}.get(batch, 30)
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle_model(n_feat, out_dim):
-    torch.manual_seed(11)
-    return gnn_ref.GINet(n_feat, out_dim, 3).eval()
-
-
-def _target(batch, name):
-    out_dim, target = TARGETS[name]
-    if target == "seed":
-        target = torch.randn(len(_datas(batch)), out_dim, generator=torch.Generator().manual_seed(5))
-    return out_dim, target
 
 
 @functools.lru_cache(maxsize=None)
 def _oracle(batch, name):
     """(out, dx, seed, node_off) of the oracle on a named batch and target (computed once)."""
-    out_dim, target = _target(batch, name)
-    return attribution_ref.oracle_input_grad(_oracle_model(_n_feat(batch), out_dim), list(_datas(batch)), target)
-
-
-@functools.lru_cache(maxsize=None)
-def _store(batch):
-    return GraphStore(pack_graphs(records_from_batch(graph_zoo.batch(_datas(batch)))), DEV)
-
-
-def _model(n_feat, out_dim):
-    m = GINet(n_feat, out_dim, 3)
-    m.load_state_dict(_oracle_model(n_feat, out_dim).state_dict())
-    return m.to(DEV)  # (left in training mode: input_gradients evaluates without dropout anyway)
+    out_dim, target = attribution_ref.target_of(batch, name)
+    return attribution_ref.oracle_input_grad(attribution_ref.oracle_model(attribution_ref.n_feat(batch), out_dim), list(attribution_ref.datas(batch)), target)
 
 
 def _run(batch, name, use_z=True, **kw):
-    out_dim, target = _target(batch, name)
+    out_dim, target = attribution_ref.target_of(batch, name)
     store = _store(batch)
     store.use_agg_x = use_z
     key = "seed" if isinstance(target, torch.Tensor) else "target"
-    res = attribution.input_gradients(_model(_n_feat(batch), out_dim), store, **{key: target}, **kw)
-    torch.cuda.synchronize()
+    try:
+        res = attribution.input_gradients(_model(attribution_ref.n_feat(batch), out_dim), store, **{key: target}, **kw)
+        torch.cuda.synchronize()
+    finally:
+        store.use_agg_x = True
     return res
 
 
@@ -128,7 +74,7 @@ def _assert_matches_oracle(res, ref, graphs=None, what=""):
 
 
 @pytest.mark.parametrize("use_z", [True, False], ids=["z", "gather"])
-@pytest.mark.parametrize("name", list(TARGETS))
+@pytest.mark.parametrize("name", list(attribution_ref.TARGETS))
 @pytest.mark.parametrize("batch", ["asym", "deg"])
 def test_input_gradients_vs_oracle(batch, name, use_z):
     res = _run(batch, name, use_z)
@@ -189,7 +135,7 @@ def test_out_equals_the_eval_forward():
 
 
 def test_gradient_is_linear_in_the_seed_exactly():
-    out_dim, seed = _target("asym", "seed")
+    out_dim, seed = attribution_ref.target_of("asym", "seed")
     store = _store("asym")
     store.use_agg_x = True
     model = _model(30, out_dim)
@@ -209,7 +155,7 @@ def test_rows_without_an_in_edge_are_exactly_zero(use_z):
         res = _run(batch, "seed", use_z)
         dx = res.dx.cpu().numpy()
         n_zero_rows = n_with_out_edges = 0
-        for g, d in enumerate(_datas(batch)):
+        for g, d in enumerate(attribution_ref.datas(batch)):
             rows = dx[res.node_off[g] : res.node_off[g + 1]]
             ei = d.edge_index.numpy()
             no_in = np.setdiff1d(np.arange(d.x.shape[0]), ei[1])
@@ -271,7 +217,7 @@ def _with_large():
     small = make_dataset(3, seed=82, n_lo=20, n_hi=60, mean_degree=6.0, k_lo=2, k_hi=13)
     datas = [data_ref.synthetic_to_data(g, f"g{j}") for j, g in enumerate([small[0], small[1], big, small[2]])]
     torch.manual_seed(11)
-    ref = attribution_ref.oracle_input_grad(_oracle_model(30, 2), datas, 1)
+    ref = attribution_ref.oracle_input_grad(attribution_ref.oracle_model(30, 2), datas, 1)
     return GraphStore(pack_graphs(records_from_batch(graph_zoo.batch(datas))), DEV), ref
 
 
@@ -295,7 +241,7 @@ def test_graph_beyond_one_workgroup_takes_the_layer_route():
 
 
 def test_nonfinite_graph_sends_its_batch_to_the_layer_route():
-    datas = [d.clone() for d in _datas("asym")]
+    datas = [d.clone() for d in attribution_ref.datas("asym")]
     datas[3].x[2, 5] = float("nan")
     store = GraphStore(pack_graphs(records_from_batch(graph_zoo.batch(datas))), DEV)
     assert store.packed.nonfinite.tolist() == [g == 3 for g in range(len(datas))]
@@ -309,6 +255,33 @@ def test_nonfinite_graph_sends_its_batch_to_the_layer_route():
     _assert_matches_oracle(split, _oracle("asym", "t1"), graphs=finite, what="split around a non-finite graph")
 
 
+@pytest.mark.parametrize("api", ["input_gradients", "integrated_gradients"])
+def test_refusals_that_need_the_store(api):
+    """What both calls refuse once they hold the store, before any launch: a
+    seed, a model or a caller's buffer that does not fit the request, and for
+    integrated gradients a per-node baseline that does not."""
+    fn, buf_kw = getattr(attribution, api), {"input_gradients": "dx_out", "integrated_gradients": "attr_out"}[api]
+    store, model = _store("asym"), _model(30, 2)
+    n, rows, xs, f = store.n_graphs, int(store.x.shape[0]), store.x_stride, store.n_feat
+    with pytest.raises(ValueError, match="seed must be"):
+        fn(model, store, seed=torch.ones(n + 1, 2))
+    with pytest.raises(ValueError, match="node features"):
+        fn(_model(33, 2), store, target=1)
+
+    def buf(r=rows, c=xs, dtype=torch.float32):
+        return torch.zeros(r, c, dtype=dtype, device=DEV)
+
+    for b in (buf(dtype=torch.float64), buf(c=xs + 4), buf(r=rows - 1), buf(c=2 * xs)[:, :xs]):  # fp64, second dimension, too few rows, not contiguous
+        with pytest.raises(ValueError, match=f"{buf_kw} must be"):
+            fn(model, store, target=1, **{buf_kw: b})
+    if api == "integrated_gradients":
+        with pytest.raises(ValueError, match="baseline must be"):
+            fn(model, store, target=1, baseline=torch.zeros(rows - 1, f))
+        twice = [0, 1, 0]
+        with pytest.raises(ValueError, match="named once"):
+            fn(model, store, indices=twice, target=1, baseline=torch.zeros(int(store._sizes[0][twice].sum()), f))  # noqa: SLF001
+
+
 # --------------------------------------------------------------------------
 # 5. scores
 # --------------------------------------------------------------------------
@@ -318,7 +291,7 @@ def test_node_scores_and_top_nodes_against_numpy():
     res = _run("asym", "t1")
     store = _store("asym")
     dx = res.dx.cpu().numpy().astype(np.float64)
-    x = np.concatenate([d.x.numpy() for d in _datas("asym")]).astype(np.float64)
+    x = np.concatenate([d.x.numpy() for d in attribution_ref.datas("asym")]).astype(np.float64)
     want = {"l2": np.sqrt((dx * dx).sum(1)), "l1": np.abs(dx).sum(1), "grad_x_input": (x * dx).sum(1)}
     for kind, w in want.items():
         s = attribution.node_scores(res, store, kind)

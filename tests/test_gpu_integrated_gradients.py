@@ -15,8 +15,6 @@ Tolerances are the suite's (``ig_ref``'s docstring): outputs rtol = atol =
 
 from __future__ import annotations
 
-import functools
-
 import numpy as np
 import pytest
 import torch
@@ -24,26 +22,16 @@ from _util import assert_grad_close
 
 import graph_zoo
 import ig_ref
+from attribution_ref import DEV
+from attribution_ref import model as _model
+from attribution_ref import store as _store
 from deeprank2_amd import _lib, attribution
 from deeprank2_amd.fused import LDS_MAX
-from deeprank2_amd.neuralnets.gnn.ginet import GINet
 from deeprank2_amd.store import GraphStore, pack_graphs, records_from_batch
 from deeprank2_amd.utils.synthetic import make_dataset
 from oracle import data_ref
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-@functools.lru_cache(maxsize=None)
-def _store(batch):
-    return GraphStore(pack_graphs(records_from_batch(graph_zoo.batch(ig_ref.datas(batch)))), DEV)
-
-
-def _model(n_feat, out_dim):
-    m = GINet(n_feat, out_dim, 3)
-    m.load_state_dict(ig_ref.oracle_model(n_feat, out_dim).state_dict())
-    return m.to(DEV)  # (left in training mode: integrated_gradients evaluates without dropout anyway)
 
 
 def _baseline(batch, kind, full=False):
@@ -232,6 +220,14 @@ def test_layer_route_agrees_with_the_reference(how, kind):
     res = _run("asym", "pred", kind, steps=4, **({"fused": False} if how == "fused_off" else {"use_z": False}))
     assert res.path == "layers"
     _assert_matches(res, ig_ref.reference("asym", "pred", kind, steps=4), what=f"layers ({how})")
+
+
+def test_layer_route_takes_a_baseline_as_a_vector_and_as_a_tensor():
+    vec, full = _run("asym", "t1", "mean", steps=4, fused=False), _run("asym", "t1", "mean", steps=4, fused=False, full=True)
+    assert vec.path == full.path == "layers"
+    for k in ("attr", "out", "out_baseline", "attr_sum", "delta"):
+        assert torch.equal(getattr(vec, k), getattr(full, k)), k
+    assert vec.attr.abs().max() > 0
 
 
 def test_nonfinite_graph_sends_its_batch_to_the_layer_route():
