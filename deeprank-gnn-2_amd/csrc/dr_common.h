@@ -65,6 +65,23 @@ inline int dr_check_pass_args(const dr_pass* p, bool has_dropout) {
   return DR_OK;
 }
 
+// Host: a dr_large_plan is usable for a batch of n_batch graphs (every
+// large-pass entry, after its own shape and LDS checks).  need_partials: the
+// family can combine per-tile partials (GINet: part_val / part_arg required,
+// part_key optional); the others combine by part_key only.
+inline int dr_check_large_plan(const dr_large_plan* plan, int32_t n_batch, bool need_partials) {
+  if (!plan || !plan->tile_first || !plan->z_row0 || !plan->tile_slot || !plan->z) return DR_E_ARG;
+  if (need_partials ? (!plan->part_val || !plan->part_arg) : !plan->part_key) return DR_E_ARG;
+  if (plan->n_tiles < n_batch || plan->k0_max < 1 || plan->k0_max > 64) return DR_E_ARG;
+  if (plan->tile_rows < 16 || plan->tile_rows > DR_LARGE_TILE || plan->tile_rows % 16) return DR_E_ARG;
+  if (plan->halo_ids && (plan->halo_max < 1 || plan->halo_max > 65535 || !plan->halo_off || !plan->lcol_off ||
+                         !plan->lcol || !plan->tile_members || !plan->tile_mptr))
+    return DR_E_ARG;
+  if (!plan->halo_ids && plan->halo_max) return DR_E_ARG;
+  if (plan->arrive) return DR_E_ARG;  // (the one-launch form was removed in r06)
+  return DR_OK;
+}
+
 // Sum over the 64 lanes of a wave (butterfly; every lane gets the total).
 __device__ __forceinline__ float dr_wave_sum(float v) {
 #pragma unroll

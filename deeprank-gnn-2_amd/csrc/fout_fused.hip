@@ -32,6 +32,7 @@
 #include <cstring>
 
 #include "graph_common.h"
+#include "large_tile.h"
 
 namespace {
 
@@ -875,8 +876,7 @@ __global__ void __launch_bounds__(NT) fout_graph_kernel(FoutArgs a) {
 //   2. one 1024-thread workgroup per graph: decode the keys into P1 / A1 and
 //      run fout_tail, reading x at the pooling args from the store and Zm / c1
 //      from plan->z.  Bit-identical to fout_graph_kernel on graphs both run.
-constexpr int NTA = 512;
-constexpr int TRF = DR_LARGE_TILE;
+// The steps the tile kernel and the tail share with GINet's are large_tile.h's.
 
 struct FoutLargeArgs {
   FoutArgs f;
@@ -898,15 +898,15 @@ __host__ __device__ inline FConvCarve fconv_carve(int N, int F, int K0, int HM, 
   o += r4(words);
   TAKE(w, c.KP * 16)
   TAKE(b1, 16)
-  TAKE(a, TRF * c.LDA)  // [x_i | Zm_i | 0] per tile row
-  TAKE(h, TRF * 16)
-  TAKE(c1, sg ? TRF : 0)
-  TAKE(m0i, HM ? TRF : N)
+  TAKE(a, TR * c.LDA)  // [x_i | Zm_i | 0] per tile row
+  TAKE(h, TR * 16)
+  TAKE(c1, sg ? TR : 0)
+  TAKE(m0i, HM ? TR : N)
   TAKE(m0p, K0 + 1)
-  TAKE(flg, TRF)  // per tile row: a depth-0 pooling arg candidate (its Zm row is stored)
+  TAKE(flg, TR)  // per tile row: a depth-0 pooling arg candidate (its Zm row is stored)
   TAKE(xh, HM * c.XS)
   TAKE(hid, HM)
-  TAKE(trp, HM ? TRF + 1 : 0)
+  TAKE(trp, HM ? TR + 1 : 0)
   // last: the tile's edges as halo indices (uint16), then (SGAT) their weights
   // at lcol + r4((ne + 8) / 2) for the tile's ne edges -- so the kernel, which
   // carves with EM = 0, places them by its own tile's edge count
@@ -923,17 +923,11 @@ __global__ void __launch_bounds__(NTA) fout_large_conv1_kernel(FoutLargeArgs la)
   const FoutArgs& a = la.f;
   const dr_large_plan& pl = la.plan;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tile = xcd_tile();
-  const int b = pl.tile_slot[tile];
-  const int t = tile - pl.tile_first[b];
-  const dr_graph_desc d = a.descs[b];
+  const TileCtx x = tile_ctx(a.descs, pl);
   const dr_graph_store& s = a.s;
-  const int g = d.gid;
-  const int64_t n0 = d.node0, ec0 = d.col0, k00 = d.k0;
-  const int N = d.n_nodes, K0 = d.n_k0, F = s.n_feat;
-  const int TRr = pl.tile_rows;
-  const int r0 = t * TRr, nrows = min(TRr, N - r0);
-  const FConvCarve c = fconv_carve(N, F, K0, pl.halo_max, 0, SG);
+  const int64_t n0 = x.d.node0, ec0 = x.d.col0;
+  const int F = s.n_feat, r0 = x.r0, nrows = x.nrows;
+  const FConvCarve c = fconv_carve(x.N, F, x.K0, pl.halo_max, 0, SG);
   const int KP = c.KP, LDA = c.LDA, XS = c.XS, ZS = la.zs;
   float* sW = lds + c.w;
   float* sB1 = lds + c.b1;
@@ -942,18 +936,8 @@ __global__ void __launch_bounds__(NTA) fout_large_conv1_kernel(FoutLargeArgs la)
   float* sC1 = lds + c.c1;
   int* sm0i = reinterpret_cast<int*>(lds + c.m0i);
   int* sm0p = reinterpret_cast<int*>(lds + c.m0p);
-  // Zm (and SGAT's c1) go to global memory only at the tile's depth-0 pooling
-  // arg candidates: the tail reads them only at the final args, tile args
-  int* sflag = reinterpret_cast<int*>(lds + c.flg);
-  for (int p = tid; p < TRr; p += NTA) sflag[p] = 0;
-  const bool compact = pl.tile_members != nullptr;
-  if (compact) {  // this tile's members by cluster (host-built), runs from tile_mptr
-    dma_copy<NTA, 4>(sm0i, pl.tile_members + (int64_t)tile * TRr, nrows);
-    dma_copy<NTA, 4>(sm0p, pl.tile_mptr + (int64_t)tile * (pl.k0_max + 1), K0 + 1);
-  } else {
-    dma_copy<NTA, 4>(sm0i, s.m0_idx + n0, N);
-    dma_copy<NTA, 4>(sm0p, s.m0_ptr + k00 + g, K0 + 1);
-  }
+  int* sflag = reinterpret_cast<int*>(lds + c.flg);  // marks the rows whose Zm (and SGAT's c1) go to plan->z
+  const bool compact = stage_pool_lists(s, pl, x, sm0i, sm0p, sflag);
   for (int p = tid; p < KP * 16; p += NTA) {  // [Wc; Wn; 0], k-major as stored
     const int k = p >> 4, o = p & 15;
     sW[p] = k < F ? a.w.wc1[k * 16 + o] : (k < 2 * F ? a.w.wn1[(k - F) * 16 + o] : 0.f);
@@ -966,7 +950,7 @@ __global__ void __launch_bounds__(NTA) fout_large_conv1_kernel(FoutLargeArgs la)
     if (k < F) sA[p] = X[(int64_t)(r0 + r) * XS + k];
     else if (k >= 2 * F) sA[p] = 0.f;
   }
-  float* zg = pl.z + (int64_t)pl.z_row0[b] * ZS;
+  float* zg = pl.z + (int64_t)pl.z_row0[x.b] * ZS;
   // Zm = D^-1 A X for the tile's rows (SGAT: Zw, c1): 8 lanes per row, 16-byte chunks
   auto gather_rows = [&](const uint16_t* col, const float* ew, const float* Xs, const int* rowp, int ebase) {
     const int nch = XS >> 2, sub = tid & 7;
@@ -991,30 +975,14 @@ __global__ void __launch_bounds__(NTA) fout_large_conv1_kernel(FoutLargeArgs la)
     int* shid = reinterpret_cast<int*>(lds + c.hid);
     uint16_t* slcol = reinterpret_cast<uint16_t*>(lds + c.lcol);
     float* sXh = lds + c.xh;
-    float* sEw;
-    const int h0 = pl.halo_off[tile], H = pl.halo_off[tile + 1] - h0;
-    dma_copy<NTA, 4>(strp, s.rowptr + n0 + g + r0, nrows + 1);
-    dma_copy<NTA, 4>(shid, pl.halo_ids + h0, H);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const int ebase = strp[0], ne = strp[nrows] - ebase;
-    sEw = lds + c.lcol + r4((ne + 8) / 2);
-    dma_copy<NTA, 16>(slcol, pl.lcol + pl.lcol_off[tile], (ne + 7) / 8);
-    if (SG) dma_copy<NTA, 4>(sEw, s.ea + ec0 + ebase, ne);  // Fe == 1: weights contiguous in CSR order
-    {
-      const int nch = XS >> 2, tot = H * nch;
-      const int wv = __builtin_amdgcn_readfirstlane(wave);
-      for (int base = wv * 64; base < tot; base += NTA)
-        if (base + lane < tot) {
-          const int hr = (base + lane) / nch, ch = base + lane - hr * nch;
-          __builtin_amdgcn_global_load_lds(DRK_AS1(X + (int64_t)shid[hr] * XS + ch * 4), DRK_AS3(sXh + base * 4), 16, 0, 0);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    gather_rows(slcol, sEw, sXh, strp, ebase);
+    const TileHalo hl = stage_halo_index(s, pl, x, strp, shid);
+    float* sEw = lds + c.lcol + r4((hl.ne + 8) / 2);
+    stage_halo_rows(pl, x, hl, shid, slcol, X, XS, sXh, [&] {
+      if (SG) dma_copy<NTA, 4>(sEw, s.ea + ec0 + hl.ebase, hl.ne);  // Fe == 1: weights contiguous in CSR order
+    }, lane, wave);
+    gather_rows(slcol, sEw, sXh, strp, hl.ebase);
   } else {  // per-edge gather of X rows from HBM / L2
-    gather_rows(s.col + ec0, SG ? s.ea + ec0 : nullptr, X, s.rowptr + n0 + g + r0, 0);
+    gather_rows(s.col + ec0, SG ? s.ea + ec0 : nullptr, X, s.rowptr + n0 + x.d.gid + r0, 0);
   }
   // (no wait for the Zm stores: the MFMA reads LDS; the tail reads Zm next launch)
   __syncthreads();
@@ -1046,40 +1014,14 @@ __global__ void __launch_bounds__(NTA) fout_large_conv1_kernel(FoutLargeArgs la)
   }
   __syncthreads();
   // the tile's share of the depth-0 max: members of each cluster inside the tile (a sub-run of its ascending list)
-  for (int p = tid; p < K0 * 16; p += NTA) {
+  for (int p = tid; p < x.K0 * 16; p += NTA) {
     const int k = p >> 4, ch = p & 15;
     int mb = sm0p[k], me = sm0p[k + 1];
-    if (!compact) {
-      int lo = mb, hi = me;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sm0i[mid] < r0) lo = mid + 1;
-        else hi = mid;
-      }
-      mb = lo;
-      hi = me;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sm0i[mid] < r0 + nrows) lo = mid + 1;
-        else hi = mid;
-      }
-      me = lo;
+    if (!compact) {  // (the second search starts where the first ended)
+      mb = lower_bound_lds(sm0i, mb, me, r0);
+      me = lower_bound_lds(sm0i, mb, me, r0 + nrows);
     }
-    float best = LOWEST;
-    int arg = N;
-    for (int m = mb; m < me; ++m) {
-      const int i = sm0i[m];
-      const float v = sH[(i - r0) * 16 + ch];
-      if (v > best) {
-        best = v;
-        arg = i;
-      }
-    }
-    if (arg < N) sflag[arg - r0] = 1;  // (benign race: every writer stores 1)
-    if (best > LOWEST)
-      __hip_atomic_fetch_max((__attribute__((address_space(1))) unsigned long long*)(pl.part_key) + ((int64_t)b * pl.k0_max + k) * 32 + ch,
-                             ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)arg),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tile_run_max<16>(pl, x, sH, sm0i, mb, me, k, ch, sflag);
   }
   // the flagged rows' Zm (from the A tile's columns F..2F-1) and c1
   __syncthreads();
@@ -1205,13 +1147,7 @@ __global__ void __launch_bounds__(NT) fout_large_tail_kernel(FoutLargeArgs la) {
   }
   for (int p = tid; p < 2048 + 64; p += NT) lds[c.fc1 + p] = p < 2048 ? a.w.fc1w[p] : a.w.fc1b[p - 2048];
   for (int p = tid; p < OUT * 65; p += NT) lds[c.fc2 + p] = p < OUT * 64 ? a.w.fc2w[p] : a.w.fc2b[p - OUT * 64];
-  for (int p = tid; p < K0 * 16; p += NT) {  // the depth-0 pool from the tiles' keys (and the keys back to zero)
-    unsigned long long* kp = reinterpret_cast<unsigned long long*>(pl.part_key) + ((int64_t)b * pl.k0_max + (p >> 4)) * 32 + (p & 15);
-    const unsigned long long key = *kp;
-    *kp = 0ull;
-    t.P1[p] = key ? __uint_as_float((uint32_t)(key >> 32)) : 0.f;
-    t.A1[p] = key ? (int)(0xffffffffu - (uint32_t)key) : N;
-  }
+  decode_keys<16, NT>(pl, b, K0, N, t.P1, t.A1);  // the depth-0 pool from the tiles' keys (and the keys back to zero)
   const int64_t counter0 = (a.p.step_counter && b == 0) ? a.p.step_counter[0] : 0;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (a.p.step_counter && b == 0 && tid == 0) a.p.step_counter[1] = counter0;  // snapshot for dr_reduce_update
@@ -1298,13 +1234,7 @@ int fout_large_family(bool sg, const dr_graph_store* store, const dr_graph_desc*
   const int XS = (store->n_feat + 3) & ~3;
   if (z_stride != (sg ? XS + 4 : XS)) return DR_E_ARG;
   if (conv_lds_bytes > 160 * 1024 || tail_lds_bytes > 160 * 1024) return DR_E_LDS;
-  if (!plan->tile_first || !plan->z_row0 || !plan->tile_slot || !plan->z || !plan->part_key) return DR_E_ARG;
-  if (plan->n_tiles < n_batch || plan->k0_max < 1 || plan->k0_max > 64 || plan->arrive) return DR_E_ARG;
-  if (plan->tile_rows < 16 || plan->tile_rows > TRF || plan->tile_rows % 16) return DR_E_ARG;
-  if (plan->halo_ids && (plan->halo_max < 1 || plan->halo_max > 65535 || !plan->halo_off || !plan->lcol_off ||
-                         !plan->lcol || !plan->tile_members || !plan->tile_mptr))
-    return DR_E_ARG;
-  if (!plan->halo_ids && plan->halo_max) return DR_E_ARG;
+  DR_CHECK(dr_check_large_plan(plan, n_batch, false));
   DR_CHECK(dr_check_pass_args(pass, false));
   if (pass->compute_dtype != DR_DTYPE_F32) return DR_E_UNSUPPORTED;
   if (n_batch == 0) return DR_OK;

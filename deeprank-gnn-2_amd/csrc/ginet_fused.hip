@@ -46,6 +46,7 @@
 #include "dr_common.h"
 #include "graph_common.h"
 #include "ginet_head.h"
+#include "large_tile.h"
 
 namespace {
 
@@ -54,7 +55,6 @@ using namespace drk;
 constexpr int NT = 1024;     // 16 waves
 constexpr int NW = NT / 64;
 constexpr int HEADW = 672;   // G64 hpre128 hh128 hd128 dh128 dG64 dout16 spare16
-typedef __attribute__((address_space(1))) unsigned long long gu64;
 
 struct Carve {
   int KP, LDW, XS;
@@ -1778,9 +1778,6 @@ __global__ void __launch_bounds__(NT) ginet_acc_kernel(GinetArgs a, const int32_
 // Graphs larger than one workgroup's LDS (atom-level: N ~ 3e3, E ~ 5e4).
 // =========================================================================
 
-constexpr int NTA = 512;  // conv1 tile kernel: 8 waves
-constexpr int TR = DR_LARGE_TILE;
-
 struct LargeArgs {
   GinetArgs g;
   dr_large_plan plan;
@@ -1826,55 +1823,30 @@ __host__ __device__ inline ConvCarve conv_carve(int N, int F, int K0, int HM, in
   return c;
 }
 
-// first position in the ascending run v[lo, hi) whose value is >= key
-__device__ __forceinline__ int lower_bound_lds(const int* v, int lo, int hi, int key) {
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (v[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// The tile's partial depth-0 max per (cluster, channel) of H (LDS, stride
-// 32, rows r0..r0+nrows-1): strict '>' in node order, first max wins, NaN never
-// enters (torch_scatter scatter_max, community_pooling.py:209).  Published by
-// 64-bit atomic max keys or per-tile partials (dr_large_plan).
-__device__ __forceinline__ void tile_partial_max(const dr_large_plan& pl, const float* sH, const int* sm0i,
-                                                 const int* sm0p, int* srng, bool compact, int tile, int b, int K0,
-                                                 int N, int r0, int nrows, int* sflag) {
+// The tile's partial depth-0 max per (cluster, channel) of H (LDS, stride 32,
+// rows r0..r0+nrows-1), see tile_run_max.  Published by 64-bit atomic max keys
+// or, without plan->part_key, as per-tile partials the tail combines in tile
+// order.  Ends with the row flags visible to the workgroup.
+__device__ __forceinline__ void tile_partial_max(const dr_large_plan& pl, const TileCtx& x, const float* sH,
+                                                 const int* sm0i, const int* sm0p, int* srng, bool compact, int* sflag) {
   const int tid = threadIdx.x;
   // each cluster's members inside this tile: a sub-run of its ascending list
-  for (int k = tid; k < K0; k += NTA) {
+  for (int k = tid; k < x.K0; k += NTA) {
     const int mb = sm0p[k], me = sm0p[k + 1];
-    srng[2 * k] = compact ? mb : lower_bound_lds(sm0i, mb, me, r0);
-    srng[2 * k + 1] = compact ? me : lower_bound_lds(sm0i, mb, me, r0 + nrows);
+    srng[2 * k] = compact ? mb : lower_bound_lds(sm0i, mb, me, x.r0);
+    srng[2 * k + 1] = compact ? me : lower_bound_lds(sm0i, mb, me, x.r0 + x.nrows);
   }
   __syncthreads();
-  for (int p = tid; p < K0 * 32; p += NTA) {
+  for (int p = tid; p < x.K0 * 32; p += NTA) {
     const int k = p >> 5, ch = p & 31;
-    float best = LOWEST;
-    int arg = N;
-    for (int m = srng[2 * k]; m < srng[2 * k + 1]; ++m) {
-      const int i = sm0i[m];
-      const float v = sH[(i - r0) * 32 + ch];
-      if (v > best) {
-        best = v;
-        arg = i;
-      }
-    }
-    if (arg < N) sflag[arg - r0] = 1;  // (benign race: every writer stores 1)
-    if (pl.part_key) {  // order-free combine over the graph's tiles (see dr_large_plan.part_key)
-      if (best > LOWEST)
-        __hip_atomic_fetch_max((gu64*)(pl.part_key) + ((int64_t)b * pl.k0_max + k) * 32 + ch,
-                               ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)arg),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      const int64_t o = ((int64_t)tile * pl.k0_max + k) * 32 + ch;
-      pl.part_val[o] = best;
-      pl.part_arg[o] = arg;
+    const RunMax m = tile_run_max<32>(pl, x, sH, sm0i, srng[2 * k], srng[2 * k + 1], k, ch, sflag);
+    if (!pl.part_key) {
+      const int64_t o = ((int64_t)x.tile * pl.k0_max + k) * 32 + ch;
+      pl.part_val[o] = m.best;
+      pl.part_arg[o] = m.arg;
     }
   }
+  __syncthreads();
 }
 
 // One tile of TR nodes: Z rows (CSR gather over HBM/L2), H = relu(Z W^T) on
@@ -1883,17 +1855,11 @@ __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
   const GinetArgs& a = la.g;
   const dr_large_plan& pl = la.plan;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tile = drk::xcd_tile();
-  const int b = pl.tile_slot[tile];
-  const int t = tile - pl.tile_first[b];
-  const dr_graph_desc d = a.descs[b];
+  const TileCtx x = tile_ctx(a.descs, pl);
   const dr_graph_store& s = a.s;
-  const int g = d.gid;
-  const int64_t n0 = d.node0, ec0 = d.col0, k00 = d.k0;
-  const int N = d.n_nodes, K0 = d.n_k0, F = s.n_feat;
-  const int TRr = pl.tile_rows;
-  const int r0 = t * TRr, nrows = min(TRr, N - r0);
-  const ConvCarve c = conv_carve(N, F, K0, pl.halo_max, 0);
+  const int64_t n0 = x.d.node0;
+  const int F = s.n_feat, TRr = pl.tile_rows, r0 = x.r0, nrows = x.nrows;
+  const ConvCarve c = conv_carve(x.N, F, x.K0, pl.halo_max, 0);
   const int KP = c.KP, LDW = c.LDW, XS = c.XS;
   float* sW1 = lds + c.w1;
   float* sZ = lds + c.z;
@@ -1901,15 +1867,10 @@ __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
   int* sm0i = reinterpret_cast<int*>(lds + c.m0i);
   int* sm0p = reinterpret_cast<int*>(lds + c.m0p);
   int* srng = reinterpret_cast<int*>(lds + c.rng);
+  int* sflag = reinterpret_cast<int*>(lds + c.flg);
+  const float* X = s.x + n0 * (int64_t)XS;
 
-  const bool compact = pl.tile_members != nullptr;
-  if (compact) {  // this tile's members by cluster (host-built), runs from tile_mptr
-    dma_copy<NTA, 4>(sm0i, pl.tile_members + (int64_t)tile * TRr, nrows);
-    dma_copy<NTA, 4>(sm0p, pl.tile_mptr + (int64_t)tile * (pl.k0_max + 1), K0 + 1);
-  } else {
-    dma_copy<NTA, 4>(sm0i, s.m0_idx + n0, N);
-    dma_copy<NTA, 4>(sm0p, s.m0_ptr + k00 + g, K0 + 1);
-  }
+  const bool compact = stage_pool_lists(s, pl, x, sm0i, sm0p, sflag);
   for (int p = tid; p < 32 * KP; p += NTA) {  // [W1; W1e] zero-padded to KP
     const int r = p / KP, k = p - r * KP;
     float v = 0.f;
@@ -1920,81 +1881,33 @@ __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
     const int r = p / (KP - XS);
     sZ[r * LDW + XS + (p - r * (KP - XS))] = 0.f;
   }
-  // Z rows go to global memory only at the tile's depth-0 pooling arg
-  // candidates (the tail reads Z at the final args, which are tile args)
-  int* sflag = reinterpret_cast<int*>(lds + c.flg);
-  for (int p = tid; p < TRr; p += NTA) sflag[p] = 0;
-  if (pl.halo_ids) {
-    // Halo path: stage the tile's rowptr slice, its halo ids, then the halo X
-    // rows and the tile's edges (as halo indices) into LDS; gather from LDS.
+  // Z = A X for the tile's rows: 8 lanes per row, 16-byte chunks of X rows
+  // summed in CSR order
+  auto gather_rows = [&](const uint16_t* col, const float* Xs, const int* rowp, int ebase) {
+    const int nch = XS >> 2, sub = tid & 7;
+    for (int r = tid >> 3; r < nrows; r += NTA / 8) {
+      const int eb = rowp[r] - ebase, ee = rowp[r + 1] - ebase;
+      for (int ch = sub; ch < nch; ch += 8) {
+        const int c4 = ch * 4;
+        const float4 acc = gather_row_chunk(col, eb, ee, Xs, XS, c4);  // (the _imm form measured +0.4 us on the halo path)
+        float* zr = sZ + r * LDW + c4;
+        zr[0] = acc.x;
+        zr[1] = acc.y;
+        zr[2] = acc.z;
+        zr[3] = acc.w;
+      }
+    }
+  };
+  if (pl.halo_ids) {  // halo path: the tile's rowptr slice, neighbour X rows and edges (as halo indices) in LDS
     int* strp = reinterpret_cast<int*>(lds + c.trp);
     int* shid = reinterpret_cast<int*>(lds + c.hid);
     uint16_t* slcol = reinterpret_cast<uint16_t*>(lds + c.lcol);
     float* sXh = lds + c.xh;
-    const int h0 = pl.halo_off[tile], H = pl.halo_off[tile + 1] - h0;
-    const int l0 = pl.lcol_off[tile];
-    dma_copy<NTA, 4>(strp, s.rowptr + n0 + g + r0, nrows + 1);
-    dma_copy<NTA, 4>(shid, pl.halo_ids + h0, H);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const int ebase = strp[0];
-    dma_copy<NTA, 16>(slcol, pl.lcol + l0, (strp[nrows] - ebase + 7) / 8);
-    {
-      const float* X = s.x + n0 * (int64_t)XS;
-      const int nch = XS >> 2, tot = H * nch;
-      const int wv = __builtin_amdgcn_readfirstlane(wave);
-      for (int base = wv * 64; base < tot; base += NTA)
-        if (base + lane < tot) {
-          const int hr = (base + lane) / nch, ch = base + lane - hr * nch;
-          __builtin_amdgcn_global_load_lds(DRK_AS1(X + (int64_t)shid[hr] * XS + ch * 4), DRK_AS3(sXh + base * 4), 16, 0, 0);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const int nch = XS >> 2, sub = tid & 7;
-    for (int r = tid >> 3; r < nrows; r += NTA / 8) {
-      const int eb = strp[r] - ebase, ee = strp[r + 1] - ebase;
-      for (int ch = sub; ch < nch; ch += 8) {
-        const int c4 = ch * 4;
-        const float4 acc = drk::gather_row_chunk(slcol, eb, ee, sXh, XS, c4);  // (the _imm form measured +0.4 us here)
-        float* zr = sZ + r * LDW + c4;
-        zr[0] = acc.x;
-        zr[1] = acc.y;
-        zr[2] = acc.z;
-        zr[3] = acc.w;
-      }
-    }
-  } else {
-  // Z = A X for the tile's rows: 8 lanes per row, 16-byte chunks of X rows.
-  {
-    const int* rp = s.rowptr + n0 + g;
-    const uint16_t* col = s.col + ec0;
-    const float* X = s.x + n0 * (int64_t)XS;
-    const int nch = XS >> 2, sub = tid & 7;
-    for (int r = tid >> 3; r < nrows; r += NTA / 8) {
-      const int i = r0 + r;
-      const int eb = rp[i], ee = rp[i + 1];
-      for (int ch = sub; ch < nch; ch += 8) {
-        const int c4 = ch * 4;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        int e = eb;
-        for (; e + 4 <= ee; e += 4) {
-          const int j0 = col[e], j1 = col[e + 1], j2 = col[e + 2], j3 = col[e + 3];
-          const float4 v0 = *reinterpret_cast<const float4*>(X + (int64_t)j0 * XS + c4);
-          const float4 v1 = *reinterpret_cast<const float4*>(X + (int64_t)j1 * XS + c4);
-          const float4 v2 = *reinterpret_cast<const float4*>(X + (int64_t)j2 * XS + c4);
-          const float4 v3 = *reinterpret_cast<const float4*>(X + (int64_t)j3 * XS + c4);
-          acc = f4add(f4add(f4add(f4add(acc, v0), v1), v2), v3);
-        }
-        for (; e < ee; ++e) acc = f4add(acc, *reinterpret_cast<const float4*>(X + (int64_t)col[e] * XS + c4));
-        float* zr = sZ + r * LDW + c4;
-        zr[0] = acc.x;
-        zr[1] = acc.y;
-        zr[2] = acc.z;
-        zr[3] = acc.w;
-      }
-    }
-  }
+    const TileHalo hl = stage_halo_index(s, pl, x, strp, shid);
+    stage_halo_rows(pl, x, hl, shid, slcol, X, XS, sXh, [] {}, lane, wave);  // (lane, wave passed: see stage_halo_rows)
+    gather_rows(slcol, sXh, strp, hl.ebase);
+  } else {  // per-edge gather of X rows from HBM / L2
+    gather_rows(s.col + x.d.col0, X, s.rowptr + n0 + x.d.gid + r0, 0);
   }
   __syncthreads();
   // H = relu(Z [W1; W1e]^T), one 16-row MFMA tile per wave
@@ -2029,9 +1942,8 @@ __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
       }
     }
   }
-  tile_partial_max(pl, sH, sm0i, sm0p, srng, compact, tile, b, K0, N, r0, nrows, sflag);
-  __syncthreads();
-  float* zg = pl.z + (int64_t)pl.z_row0[b] * XS;
+  tile_partial_max(pl, x, sH, sm0i, sm0p, srng, compact, sflag);
+  float* zg = pl.z + (int64_t)pl.z_row0[x.b] * XS;
   const int nch = XS >> 2;
   for (int p = tid; p < nrows * nch; p += NTA) {
     const int r = p / nch, c4 = (p - r * nch) * 4;
@@ -2114,17 +2026,11 @@ __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) 
   const GinetArgs& a = la.g;
   const dr_large_plan& pl = la.plan;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tile = drk::xcd_tile();
-  const int b = pl.tile_slot[tile];
-  const int t = tile - pl.tile_first[b];
-  const dr_graph_desc d = a.descs[b];
+  const TileCtx x = tile_ctx(a.descs, pl);
   const dr_graph_store& s = a.s;
-  const int g = d.gid;
-  const int64_t n0 = d.node0, ec0 = d.col0, k00 = d.k0;
-  const int N = d.n_nodes, K0 = d.n_k0, F = s.n_feat;
-  const int TRr = pl.tile_rows;
-  const int r0 = t * TRr, nrows = min(TRr, N - r0);
-  const ConvCarveB c = conv_carve_bf16(N, F, K0, pl.halo_max, 0);
+  const int64_t n0 = x.d.node0;
+  const int F = s.n_feat, TRr = pl.tile_rows, r0 = x.r0, nrows = x.nrows;
+  const ConvCarveB c = conv_carve_bf16(x.N, F, x.K0, pl.halo_max, 0);
   const int KPB = c.KPB, ZSB = c.ZSB, XSB = s.x_bf16_stride;
   uint16_t* sW = reinterpret_cast<uint16_t*>(lds + c.w1);
   uint16_t* sZ = reinterpret_cast<uint16_t*>(lds + c.z);
@@ -2132,17 +2038,11 @@ __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) 
   int* sm0i = reinterpret_cast<int*>(lds + c.m0i);
   int* sm0p = reinterpret_cast<int*>(lds + c.m0p);
   int* srng = reinterpret_cast<int*>(lds + c.rng);
+  int* sflag = reinterpret_cast<int*>(lds + c.flg);
   const uint16_t* X = s.x_bf16 + n0 * (int64_t)XSB;
-  uint16_t* zg = reinterpret_cast<uint16_t*>(pl.z) + (int64_t)pl.z_row0[b] * XSB;
+  uint16_t* zg = reinterpret_cast<uint16_t*>(pl.z) + (int64_t)pl.z_row0[x.b] * XSB;
 
-  const bool compact = pl.tile_members != nullptr;
-  if (compact) {
-    dma_copy<NTA, 4>(sm0i, pl.tile_members + (int64_t)tile * TRr, nrows);
-    dma_copy<NTA, 4>(sm0p, pl.tile_mptr + (int64_t)tile * (pl.k0_max + 1), K0 + 1);
-  } else {
-    dma_copy<NTA, 4>(sm0i, s.m0_idx + n0, N);
-    dma_copy<NTA, 4>(sm0p, s.m0_ptr + k00 + g, K0 + 1);
-  }
+  const bool compact = stage_pool_lists(s, pl, x, sm0i, sm0p, sflag);
   for (int p = tid; p < 32 * KPB; p += NTA) {  // [W1; W1e] in bf16, K zero-padded to KPB
     const int r = p / KPB, k = p - r * KPB;
     float v = 0.f;
@@ -2153,8 +2053,6 @@ __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) 
     const int r = p / (KPB - XSB);
     sZ[r * ZSB + XSB + (p - r * (KPB - XSB))] = 0;
   }
-  int* sflag = reinterpret_cast<int*>(lds + c.flg);  // (as conv_tile_f32)
-  for (int p = tid; p < TRr; p += NTA) sflag[p] = 0;
   // Z = A X for the tile's rows: 8 lanes per row, 4 bf16 (8 bytes) per lane
   // and edge, summed in fp32 in CSR order; rounded to bf16 once per row.
   const int nch = XSB >> 2, sub = tid & 7;
@@ -2163,25 +2061,9 @@ __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) 
     int* shid = reinterpret_cast<int*>(lds + c.hid);
     uint16_t* slcol = reinterpret_cast<uint16_t*>(lds + c.lcol);
     uint16_t* sXh = reinterpret_cast<uint16_t*>(lds + c.xh);
-    const int h0 = pl.halo_off[tile], H = pl.halo_off[tile + 1] - h0;
-    const int l0 = pl.lcol_off[tile];
-    dma_copy<NTA, 4>(strp, s.rowptr + n0 + g + r0, nrows + 1);
-    dma_copy<NTA, 4>(shid, pl.halo_ids + h0, H);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const int ebase = strp[0];
-    dma_copy<NTA, 16>(slcol, pl.lcol + l0, (strp[nrows] - ebase + 7) / 8);
-    {  // halo rows: 16-byte DMA lanes, XSB/8 per row
-      const int n16 = XSB >> 3, tot = H * n16;
-      const int wv = __builtin_amdgcn_readfirstlane(wave);
-      for (int base = wv * 64; base < tot; base += NTA)
-        if (base + lane < tot) {
-          const int hr = (base + lane) / n16, q = base + lane - hr * n16;
-          __builtin_amdgcn_global_load_lds(DRK_AS1(X + (int64_t)shid[hr] * XSB + q * 8), DRK_AS3(sXh + base * 8), 16, 0, 0);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    const TileHalo hl = stage_halo_index(s, pl, x, strp, shid);
+    stage_halo_rows(pl, x, hl, shid, slcol, X, XSB, sXh);
+    const int ebase = hl.ebase;
     for (int r = tid >> 3; r < nrows; r += NTA / 8) {
       const int eb = strp[r] - ebase, ee = strp[r + 1] - ebase;
       for (int ch = sub; ch < nch; ch += 8) {
@@ -2204,8 +2086,8 @@ __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) 
       }
     }
   } else {
-    const int* rp = s.rowptr + n0 + g;
-    const uint16_t* col = s.col + ec0;
+    const int* rp = s.rowptr + n0 + x.d.gid;
+    const uint16_t* col = s.col + x.d.col0;
     for (int r = tid >> 3; r < nrows; r += NTA / 8) {
       const int i = r0 + r;
       const int eb = rp[i], ee = rp[i + 1];
@@ -2253,8 +2135,7 @@ __device__ __forceinline__ void conv_tile_bf16(const LargeArgs& la, float* lds) 
       }
     }
   }
-  tile_partial_max(pl, sH, sm0i, sm0p, srng, compact, tile, b, K0, N, r0, nrows, sflag);
-  __syncthreads();
+  tile_partial_max(pl, x, sH, sm0i, sm0p, srng, compact, sflag);
   for (int p = tid; p < nrows * nch; p += NTA) {
     const int r = p / nch, c4 = (p - r * nch) * 4;
     if (sflag[r]) *reinterpret_cast<uint2*>(zg + (int64_t)(r0 + r) * XSB + c4) = *reinterpret_cast<const uint2*>(&sZ[r * ZSB + c4]);
@@ -2313,15 +2194,8 @@ __device__ __forceinline__ void tail_body(const LargeArgs& la, int b, float* lds
   STAMP(1);
   // tiles in node order, strict '>': the first maximum over the whole graph
   const int tb = pl.tile_first[b], te = pl.tile_first[b + 1];
-  if (pl.part_key) {
-    for (int p = tid; p < K0 * 32; p += NT) {
-      unsigned long long* kp = reinterpret_cast<unsigned long long*>(pl.part_key) + (int64_t)b * pl.k0_max * 32 + p;
-      const unsigned long long key = *kp;
-      *kp = 0ull;  // ready for the next pass
-      t.p1[p] = key ? __uint_as_float((uint32_t)(key >> 32)) : 0.f;
-      t.a1[p] = key ? (int)(0xffffffffu - (uint32_t)key) : N;
-    }
-  } else
+  if (pl.part_key) decode_keys<32, NT>(pl, b, K0, N, t.p1, t.a1);
+  else
   for (int p = tid; p < K0 * 32; p += NT) {
     float best = LOWEST;
     int arg = N;
@@ -2844,15 +2718,7 @@ extern "C" int dr_ginet_large_pass(const dr_graph_store* store, const dr_graph_d
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
   if (store->n_feat < 1 || store->n_feat > 64) return DR_E_UNSUPPORTED;
   if (conv_lds_bytes > 160 * 1024 || tail_lds_bytes > 160 * 1024) return DR_E_LDS;
-  if (!plan->tile_first || !plan->z_row0 || !plan->tile_slot || !plan->z || !plan->part_val || !plan->part_arg)
-    return DR_E_ARG;
-  if (plan->n_tiles < n_batch || plan->k0_max < 1 || plan->k0_max > 64) return DR_E_ARG;
-  if (plan->tile_rows < 16 || plan->tile_rows > TR || plan->tile_rows % 16) return DR_E_ARG;
-  if (plan->halo_ids && (plan->halo_max < 1 || plan->halo_max > 65535 || !plan->halo_off || !plan->lcol_off ||
-                         !plan->lcol || !plan->tile_members || !plan->tile_mptr))
-    return DR_E_ARG;
-  if (!plan->halo_ids && plan->halo_max) return DR_E_ARG;
-  if (plan->arrive) return DR_E_ARG;  // (the one-launch form was removed in r06)
+  DR_CHECK(dr_check_large_plan(plan, n_batch, true));
   DR_CHECK(dr_check_pass_args(pass, true));
   const bool bf16 = pass->compute_dtype == DR_DTYPE_BF16;
   if (pass->compute_dtype != DR_DTYPE_F32 && !bf16) return DR_E_ARG;

@@ -266,45 +266,6 @@ __device__ __forceinline__ void gather_two_row_chunks(const uint16_t* col, int e
   out1 = a1;
 }
 
-// As gather_two_row_chunks with the column ids pre-scaled to byte offsets of
-// X rows (col[e] = j * XS * 4, so rows up to 64 KiB into X): one add per edge
-// and lane forms the address (same sums, same order).
-__device__ __forceinline__ void gather_two_row_chunks_boff(const uint16_t* col, int eb0, int ee0, int eb1, int ee1,
-                                                           const char* Xc, float4& out0, float4& out1) {
-  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-  int e0 = eb0, e1 = eb1;
-#define DRK_XR(off) (*reinterpret_cast<const float4*>(Xc + (off)))
-  for (; e0 + 4 <= ee0 && e1 + 4 <= ee1; e0 += 4, e1 += 4) {
-    int f1 = e0 + 1, f2 = e0 + 2, f3 = e0 + 3, g1 = e1 + 1, g2 = e1 + 2, g3 = e1 + 3;
-    asm volatile("" : "+v"(f1), "+v"(f2), "+v"(f3), "+v"(g1), "+v"(g2), "+v"(g3));
-    const uint32_t j0 = col[e0], j1 = col[f1], j2 = col[f2], j3 = col[f3];
-    const uint32_t k0 = col[e1], k1 = col[g1], k2 = col[g2], k3 = col[g3];
-    const float4 v0 = DRK_XR(j0), v1 = DRK_XR(j1), v2 = DRK_XR(j2), v3 = DRK_XR(j3);
-    const float4 w0 = DRK_XR(k0), w1 = DRK_XR(k1), w2 = DRK_XR(k2), w3 = DRK_XR(k3);
-    a0 = f4add(f4add(f4add(f4add(a0, v0), v1), v2), v3);
-    a1 = f4add(f4add(f4add(f4add(a1, w0), w1), w2), w3);
-  }
-  for (; e0 + 4 <= ee0; e0 += 4) {
-    int f1 = e0 + 1, f2 = e0 + 2, f3 = e0 + 3;
-    asm volatile("" : "+v"(f1), "+v"(f2), "+v"(f3));
-    const uint32_t j0 = col[e0], j1 = col[f1], j2 = col[f2], j3 = col[f3];
-    const float4 v0 = DRK_XR(j0), v1 = DRK_XR(j1), v2 = DRK_XR(j2), v3 = DRK_XR(j3);
-    a0 = f4add(f4add(f4add(f4add(a0, v0), v1), v2), v3);
-  }
-  for (; e1 + 4 <= ee1; e1 += 4) {
-    int g1 = e1 + 1, g2 = e1 + 2, g3 = e1 + 3;
-    asm volatile("" : "+v"(g1), "+v"(g2), "+v"(g3));
-    const uint32_t k0 = col[e1], k1 = col[g1], k2 = col[g2], k3 = col[g3];
-    const float4 w0 = DRK_XR(k0), w1 = DRK_XR(k1), w2 = DRK_XR(k2), w3 = DRK_XR(k3);
-    a1 = f4add(f4add(f4add(f4add(a1, w0), w1), w2), w3);
-  }
-  for (; e0 < ee0; ++e0) a0 = f4add(a0, DRK_XR((uint32_t)col[e0]));
-  for (; e1 < ee1; ++e1) a1 = f4add(a1, DRK_XR((uint32_t)col[e1]));
-#undef DRK_XR
-  out0 = a0;
-  out1 = a1;
-}
-
 }  // namespace drk
 
 #ifdef DR_STAMPS

@@ -64,17 +64,24 @@ def test_large_path_bit_identical_to_single_workgroup_kernel(name):
     model = (foutnet.FoutNet if name == "foutnet" else sgat.SGAT)(30, 2, fe).to(DEV)
     params = model.ordered_params()
     res = []
-    for force, halos in ((False, True), (True, True), (True, False)):
+    # (force, halos, tile rows): the default tile (64), then 16 (every cluster
+    # straddles tiles, most graphs end in a short tile) and 128 (some graphs are one tile)
+    cases = [(False, True, None), (True, True, None), (True, False, None)]
+    cases += [(True, halos, tile) for tile in (16, 128) for halos in (True, False)]
+    for force, halos, tile in cases:
         h = BatchHandle(store, np.arange(12))
-        h.force_large, h.large_halos = force, halos
-        out = torch.empty(12, 2, device=DEV)
-        slab = torch.empty(12 * foutnet.slab_stride(30), device=DEV)  # SGAT shares FoutNet's partial layout
-        head = torch.zeros(12 * foutnet.head_stride(2), device=DEV)
-        lpg = torch.empty(12, device=DEV)
-        store.set_targets(np.arange(12) % 2)
-        mod.graph_pass(h, params, 2, 3, loss_kind=_lib.DR_LOSS_CE, loss_scale=1 / 12, out=out, loss_per_graph=lpg, slab=slab, head=head)
-        torch.cuda.synchronize()
-        res.append((out.cpu(), slab.cpu(), head.cpu(), lpg.cpu()))
+        h.force_large, h.large_halos, h.large_tile = force, halos, tile
+        for _ in range(2):  # the second pass on the handle's plan finds the max keys back at zero
+            out = torch.empty(12, 2, device=DEV)
+            slab = torch.empty(12 * foutnet.slab_stride(30), device=DEV)  # SGAT shares FoutNet's partial layout
+            head = torch.zeros(12 * foutnet.head_stride(2), device=DEV)
+            lpg = torch.empty(12, device=DEV)
+            store.set_targets(np.arange(12) % 2)
+            mod.graph_pass(h, params, 2, 3, loss_kind=_lib.DR_LOSS_CE, loss_scale=1 / 12, out=out, loss_per_graph=lpg, slab=slab, head=head)
+            torch.cuda.synchronize()
+            res.append((out.cpu(), slab.cpu(), head.cpu(), lpg.cpu()))
+        if force:
+            assert h.large_plan(2, kind="fout" if name == "foutnet" else "sgat").TILE == (tile or 64)
     for other in res[1:]:
         for x, y in zip(res[0], other):
             assert torch.equal(x, y)

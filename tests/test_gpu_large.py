@@ -53,19 +53,28 @@ def test_large_path_bit_identical_to_single_workgroup_kernel():
     model = amd.GINet(30, 2, 3).to(DEV)
     params = model.ordered_params()
     res = []
-    for force, halos, amax in ((False, True, True), (True, True, True), (True, False, True), (True, True, False), (True, False, False)):
+    # (force, halos, atomic max, tile rows): the default tile (64), then 16 (every
+    # cluster straddles tiles, most graphs end in a short tile) and 128 (some
+    # graphs are one tile)
+    cases = [(False, True, True, None), (True, True, True, None), (True, False, True, None), (True, True, False, None), (True, False, False, None)]
+    cases += [(True, halos, amax, tile) for tile in (16, 128) for halos, amax in ((True, True), (False, True), (True, False), (False, False))]
+    for force, halos, amax, tile in cases:
         h = BatchHandle(store, np.arange(16))
         h.force_large = force
         h.large_halos = halos
         h.large_atomic_max = amax
-        out = torch.empty(16, 2, device=DEV)
-        slab = torch.empty(16 * amd.slab_stride(30), device=DEV)
-        head = torch.zeros(16 * amd.head_stride(2), device=DEV)
-        lpg = torch.empty(16, device=DEV)
-        store.set_targets(np.arange(16) % 2)
-        amd.graph_pass(h, params, 2, 3, loss_kind=_lib.DR_LOSS_CE, loss_scale=1 / 16, dropout=Dropout(0.4, seed=7, offset=3), out=out, loss_per_graph=lpg, slab=slab, head=head)
-        torch.cuda.synchronize()
-        res.append((out.cpu(), slab.cpu(), head.cpu(), lpg.cpu()))
+        h.large_tile = tile
+        for _ in range(2):  # the second pass on the handle's plan finds the max keys back at zero
+            out = torch.empty(16, 2, device=DEV)
+            slab = torch.empty(16 * amd.slab_stride(30), device=DEV)
+            head = torch.zeros(16 * amd.head_stride(2), device=DEV)
+            lpg = torch.empty(16, device=DEV)
+            store.set_targets(np.arange(16) % 2)
+            amd.graph_pass(h, params, 2, 3, loss_kind=_lib.DR_LOSS_CE, loss_scale=1 / 16, dropout=Dropout(0.4, seed=7, offset=3), out=out, loss_per_graph=lpg, slab=slab, head=head)
+            torch.cuda.synchronize()
+            res.append((out.cpu(), slab.cpu(), head.cpu(), lpg.cpu()))
+        if force:
+            assert h.large_plan(2).TILE == (tile or 64)
     for other in res[1:]:  # split path with tile halos in LDS, and with the per-edge HBM gather
         for x, y in zip(res[0], other):
             assert torch.equal(x, y)
