@@ -2253,6 +2253,85 @@ __global__ void __launch_bounds__(NT) ginet_large_tail_kernel(LargeArgs la) {
   tail_body(la, blockIdx.x, lds);
 }
 
+// ---- input gradients on the large path (dr_ginet_large_input_grad_pass) ----
+// ginet_input_grad_kernel's epilogue cut at its barrier: the tail forms dZ in
+// a global workspace (dz: graph b's rows of DS = r4(F) words from row
+// plan.z_row0[b]), and a tile kernel gathers dX = A^T dZ from it.
+//
+// Tail: tail_body as it is, then ginet_input_grad_kernel's loop on the global
+// rows: one thread per (cluster k, feature f) runs
+//   dZ[a1[k, ch], f] = fmaf(dp1[k, ch], [W1; W1e][ch, f], dZ[a1[k, ch], f]),  ch = 0 .. 31,
+// as 32 read-modify-writes in channel order (the loads hit the words this
+// thread stored, or the workgroup's zeros).  No two threads touch one word (k
+// fixes the node's cluster, f the column), and the loop runs over all K0 F
+// items (K0 <= 64: up to four per thread).  The graph's dz rows are zeroed by
+// the workgroup before tail_body.  A form that sorted each cluster's
+// (node, channel) pairs and stored every touched word once from a register
+// measured level with this one and was not kept.
+__global__ void __launch_bounds__(NT) ginet_large_input_grad_tail_kernel(LargeArgs la, float* dz) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int F = la.g.s.n_feat, DS = r4(F);
+  float* dzg = dz + (int64_t)la.plan.z_row0[b] * DS;
+  {  // early: nothing reads dz before the loop below
+    const int n4 = la.g.descs[b].n_nodes * (DS >> 2);
+    float4* z4 = reinterpret_cast<float4*>(dzg);
+    for (int p = tid; p < n4; p += NT) z4[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  tail_body(la, b, lds);
+  __syncthreads();  // the tail's last step (dW1) has read Z; dp1 / a1 are complete, the zeros above are stored
+  const dr_graph_desc d = la.g.descs[b];
+  const int N = d.n_nodes, K0 = d.n_k0;
+  const TailCarve c = tail_carve(K0, d.n_p1, d.n_k1, la.g.s.transpose_aliased, la.g.p.out_dim);
+  const float* dp1 = lds + c.dp1;
+  const int* a1 = reinterpret_cast<const int*>(lds + c.a1);
+  for (int p = tid; p < K0 * F; p += NT) {
+    const int k = p / F, f = p - k * F;
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const float* wsrc = (hf ? la.g.w.w1e : la.g.w.w1) + f;
+      float w[16], v[16];
+      int i[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) w[u] = wsrc[u * F];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int4 iv = *reinterpret_cast<const int4*>(a1 + k * 32 + hf * 16 + 4 * q);
+        const float4 vv = *reinterpret_cast<const float4*>(dp1 + k * 32 + hf * 16 + 4 * q);
+        i[4 * q] = iv.x; i[4 * q + 1] = iv.y; i[4 * q + 2] = iv.z; i[4 * q + 3] = iv.w;
+        v[4 * q] = vv.x; v[4 * q + 1] = vv.y; v[4 * q + 2] = vv.z; v[4 * q + 3] = vv.w;
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (i[u] < N) dzg[i[u] * DS + f] = fmaf(v[u], w[u], dzg[i[u] * DS + f]);
+    }
+  }
+}
+
+// dX[m, :] = sum over transposed CSR row m, in slot order from +0, of dZ[t_col[s], :]
+// for the rows of one tile: 8 lanes per row, one 16-byte chunk each, dz read
+// from global memory (a graph's block stays in its tiles' L2: tile_ctx);
+// zeros past r4(F).
+__global__ void __launch_bounds__(NTA) ginet_large_dx_kernel(LargeArgs la, dr_input_grad ig, const float* dz) {
+  const dr_graph_store& s = la.g.s;
+  const TileCtx x = tile_ctx(la.g.descs, la.plan);
+  const int tid = threadIdx.x, DS = r4(s.n_feat);
+  const int* trp = s.t_rowptr + x.d.node0 + x.d.gid + x.r0;
+  const uint16_t* tcol = s.t_col + x.d.col0;
+  const float* dzg = dz + (int64_t)la.plan.z_row0[x.b] * DS;
+  float* out = ig.dx + (ig.row_off[x.b] + x.r0) * (int64_t)ig.dx_stride;
+  const int sub = tid & 7, nchd = DS >> 2, ncho = ig.dx_stride >> 2;
+  for (int r = tid >> 3; r < x.nrows; r += NTA / 8) {
+    const int eb = trp[r], ee = trp[r + 1];
+    float* row = out + r * (int64_t)ig.dx_stride;
+    for (int ch = sub; ch < ncho; ch += 8) {
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (ch < nchd) acc = drk::gather_row_chunk(tcol, eb, ee, dzg, DS, ch * 4);
+      *reinterpret_cast<float4*>(row + ch * 4) = acc;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int64_t dr_ginet_lds_bytes(int32_t n_nodes, int32_t n_edges, int32_t n_feat, int32_t k0, int32_t p1_edges,
@@ -2710,9 +2789,10 @@ extern "C" int64_t dr_ginet_tail_lds_bytes(int32_t k0, int32_t p1_edges, int32_t
   return 4LL * tail_carve(k0, p1_edges, k1, transpose_aliased, out_dim).total;
 }
 
-extern "C" int dr_ginet_large_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
-                                   const dr_large_plan* plan, const dr_ginet_weights* w, const dr_pass* pass,
-                                   int32_t conv_lds_bytes, int32_t tail_lds_bytes, void* stream) {
+// What dr_ginet_large_pass and dr_ginet_large_input_grad_pass check before anything is launched
+static int large_pass_check(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                            const dr_large_plan* plan, const dr_ginet_weights* w, const dr_pass* pass,
+                            int32_t conv_lds_bytes, int32_t tail_lds_bytes, bool f32_only) {
   if (!store || !descs || !w || !pass || !plan || n_batch < 0) return DR_E_ARG;
   DR_CHECK(dr_check_loss(pass));
   if (pass->out_dim < 1 || pass->out_dim > DR_MAX_OUT) return DR_E_UNSUPPORTED;
@@ -2721,8 +2801,17 @@ extern "C" int dr_ginet_large_pass(const dr_graph_store* store, const dr_graph_d
   DR_CHECK(dr_check_large_plan(plan, n_batch, true));
   DR_CHECK(dr_check_pass_args(pass, true));
   const bool bf16 = pass->compute_dtype == DR_DTYPE_BF16;
+  if (f32_only && pass->compute_dtype != DR_DTYPE_F32) return DR_E_UNSUPPORTED;
   if (pass->compute_dtype != DR_DTYPE_F32 && !bf16) return DR_E_ARG;
   if (bf16 && (!store->x_bf16 || store->x_bf16_stride < store->n_feat || store->x_bf16_stride % 8)) return DR_E_ARG;
+  return DR_OK;
+}
+
+extern "C" int dr_ginet_large_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                                   const dr_large_plan* plan, const dr_ginet_weights* w, const dr_pass* pass,
+                                   int32_t conv_lds_bytes, int32_t tail_lds_bytes, void* stream) {
+  DR_CHECK(large_pass_check(store, descs, n_batch, plan, w, pass, conv_lds_bytes, tail_lds_bytes, false));
+  const bool bf16 = pass->compute_dtype == DR_DTYPE_BF16;
   if (n_batch == 0) return DR_OK;
   DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_large_conv1_kernel)));
   DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_large_conv1_bf16_kernel)));
@@ -2740,6 +2829,35 @@ extern "C" int dr_ginet_large_pass(const dr_graph_store* store, const dr_graph_d
   else
     hipLaunchKernelGGL(ginet_large_conv1_kernel, dim3(plan->n_tiles), dim3(NTA), conv_lds_bytes, st, la);
   hipLaunchKernelGGL(ginet_large_tail_kernel, dim3(n_batch), dim3(NT), tail_lds_bytes, st, la);
+  return (int)hipGetLastError();
+}
+
+extern "C" int dr_ginet_large_input_grad_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                                              const dr_large_plan* plan, const dr_ginet_weights* w, const dr_pass* pass,
+                                              const dr_input_grad* ig, float* dz, int32_t conv_lds_bytes,
+                                              int32_t tail_lds_bytes, void* stream) {
+  DR_CHECK(large_pass_check(store, descs, n_batch, plan, w, pass, conv_lds_bytes, tail_lds_bytes, true));
+  if (!(pass->flags & DR_PASS_BACKWARD)) return DR_E_ARG;
+  if (pass->slot || pass->step_counter) return DR_E_ARG;
+  if (!ig || !ig->dx || !ig->row_off || !dz) return DR_E_ARG;
+  if (ig->dx_stride < store->n_feat || ig->dx_stride % 4 != 0) return DR_E_ARG;
+  if (reinterpret_cast<uintptr_t>(ig->dx) % 16 != 0 || reinterpret_cast<uintptr_t>(dz) % 16 != 0) return DR_E_ARG;
+  if (!store->cl0 || !store->t_rowptr || !store->t_col) return DR_E_ARG;
+  if (n_batch == 0) return DR_OK;
+  DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_large_conv1_kernel)));
+  DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_large_input_grad_tail_kernel)));
+  LargeArgs la;
+  la.g.s = *store;
+  la.g.w = *w;
+  la.g.p = *pass;
+  la.g.descs = descs;
+  la.g.B = n_batch;
+  la.plan = *plan;
+  const dr_input_grad iga = *ig;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(ginet_large_conv1_kernel, dim3(plan->n_tiles), dim3(NTA), conv_lds_bytes, st, la);
+  hipLaunchKernelGGL(ginet_large_input_grad_tail_kernel, dim3(n_batch), dim3(NT), tail_lds_bytes, st, la, dz);
+  hipLaunchKernelGGL(ginet_large_dx_kernel, dim3(plan->n_tiles), dim3(NTA), 0, st, la, iga, static_cast<const float*>(dz));
   return (int)hipGetLastError();
 }
 

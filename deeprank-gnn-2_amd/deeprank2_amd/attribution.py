@@ -19,6 +19,13 @@ graph beyond one workgroup's LDS, or ``fused=False`` — run
 ``layered.ginet_forward`` with ``x`` requiring grad and ``torch.autograd.grad``
 (``result.path`` says which route the batches took).
 
+Graphs beyond one workgroup's LDS (atom-level graphs) have a fused route of
+their own, ``dr_ginet_large_input_grad_pass``: the large-graph path's tile
+kernel and per-graph tail, ``dZ`` formed by the tail in a global workspace, and
+a tile kernel for ``dX = A^T dZ``; the same bits as the single-workgroup pass on
+graphs both take.  It is opt-in (``input_gradients(..., tiles=True)``,
+``TILES_DEFAULT``).
+
 ``integrated_gradients`` integrates that gradient along the straight path from
 a baseline to ``x`` (Sundararajan et al. 2017): on the reference model, one
 ``torch.autograd.grad`` per quadrature node, weighted and summed, times
@@ -48,6 +55,12 @@ from deeprank2_amd.store import store_of
 # measurement behind the choice: DESIGN §5, profiles/attribution/)
 FUSED_DEFAULT = True
 
+# Whether batches beyond one workgroup's LDS run dr_ginet_large_input_grad_pass
+# by default (opt-in until the default is decided on DESIGN §5 "Input gradients
+# on tiles", profiles/attribution_large/)
+TILES_DEFAULT = False
+K0_TILES_MAX = 64  # most depth-0 clusters of a graph on the large-graph path (LargePlan)
+
 SCORE_KINDS = ("l2", "l1", "grad_x_input")
 
 
@@ -70,7 +83,7 @@ class InputGradients(_NodeRows):
     seed: torch.Tensor  # [n, out_dim] the upstream gradient each graph was seeded with
     node_off: np.ndarray  # host int64 [n + 1]: graph i's rows are node_off[i] .. node_off[i + 1] - 1
     indices: np.ndarray  # host int64 [n]: the graphs' positions in the store
-    path: str  # "fused", "layers" or "mixed"
+    path: str  # "fused", "tiles", "layers" or "mixed" (more than one route)
 
 
 def batch_rows(n_nodes, indices, batch_size):
@@ -117,6 +130,16 @@ def _check_target(name, model, target, seed):
     elif isinstance(target, (bool, float)) or not isinstance(target, (int, np.integer)) or not 0 <= int(target) < out_dim:
         msg = f"target must lie in 0..{out_dim - 1} (got {target!r})"
         raise ValueError(msg)
+
+
+def _check_tiles(tiles):
+    """``input_gradients``' ``tiles`` as False, True or "force" (needs no device)."""
+    if tiles is None:
+        tiles = TILES_DEFAULT
+    if tiles is True or tiles is False or (isinstance(tiles, str) and tiles == "force"):
+        return tiles
+    msg = f"tiles must be None, False, True or 'force' (got {tiles!r})"
+    raise ValueError(msg)
 
 
 def _one_hot_pred(out):
@@ -211,21 +234,51 @@ def _layer_grad(model, t, x, seed, pred=False):
     return o.detach(), g
 
 
-def _input_grad_fused(rq: _Request, c, h: BatchHandle, s, e, z, zs):
-    """One ``dr_ginet_input_grad_pass`` launch: the batch's rows of ``dx`` in place."""
+def _input_grad_args(rq: _Request, c, h: BatchHandle, s, e):
+    """What the two fused routes hand their entry alike: the pass (seeded; for
+    ``"pred"`` after one forward through the eval path and the one-hot on the
+    device) and the ``dr_input_grad`` of the batch's rows."""
     out_dim, dev = rq.out_dim, rq.dev
     if c.slab is None:
         c.slab = torch.empty(rq.bmax * ginet.slab_stride(rq.f), dtype=torch.float32, device=dev)
         c.head = torch.zeros(rq.bmax * ginet.head_stride(out_dim), dtype=torch.float32, device=dev)
-    if rq.target == "pred":  # one forward through the eval path, then the one-hot on the device
+    if rq.target == "pred":
         ginet.graph_pass(h, rq.params, out_dim, _lib.DR_PASS_FORWARD, out=rq.out[s:e])
         rq.seed_t[s:e] = _one_hot_pred(rq.out[s:e])
     p = make_pass(out_dim, _lib.DR_PASS_FORWARD | _lib.DR_PASS_BACKWARD, dout=rq.seed_t[s:e], out=rq.out[s:e], slab=c.slab, head=c.head)
     ig = _lib.InputGradC()
     ig.dx, ig.row_off, ig.dx_stride = rq.buf.data_ptr(), c.row_off.data_ptr() + 8 * s, rq.xs
+    return p, ig
+
+
+def _input_grad_fused(rq: _Request, c, h: BatchHandle, s, e, z, zs):
+    """One ``dr_ginet_input_grad_pass`` launch: the batch's rows of ``dx`` in place."""
+    out_dim, dev = rq.out_dim, rq.dev
+    p, ig = _input_grad_args(rq, c, h, s, e)
     lds = _lds("dr_ginet_input_grad_lds_bytes", h, out_dim, zs)
     rc = _lib.load().dr_ginet_input_grad_pass(rq.store.cstruct(), h.descs.data_ptr(), h.B, rq.w, p, ig, _lib.ptr(z), zs, lds, _lib.stream_ptr(dev))
     _lib.check(rc, "dr_ginet_input_grad_pass")
+
+
+def _tile_plan(rq: _Request, h: BatchHandle):
+    """The batch's ``dr_large_plan`` if it passes the tile checks (an fp32
+    store on the fused route, no non-finite graph, every graph within
+    ``K0_TILES_MAX`` clusters, the plan's LDS within one workgroup's), else None."""
+    if not rq.kernel_ok or h.nonfinite or h.max_sizes[2] > K0_TILES_MAX:
+        return None
+    try:
+        return h.large_plan(rq.out_dim)
+    except RuntimeError:  # LargePlan's refusal: a tile or the tail beyond 160 KiB of LDS
+        return None
+
+
+def _input_grad_tiles(rq: _Request, c, h: BatchHandle, plan, s, e):
+    """One ``dr_ginet_large_input_grad_pass`` (three launches): the batch's rows of ``dx`` in place."""
+    if c.dz is None:  # dZ of the largest batch, rows of r4(F) words
+        c.dz = torch.empty(max(c.rmax, 1) * (-(-rq.f // 4) * 4), dtype=torch.float32, device=rq.dev)
+    p, ig = _input_grad_args(rq, c, h, s, e)
+    rc = _lib.load().dr_ginet_large_input_grad_pass(rq.store.cstruct(), h.descs.data_ptr(), h.B, plan.c, rq.w, p, ig, c.dz.data_ptr(), plan.conv_lds, plan.tail_lds, _lib.stream_ptr(rq.dev))
+    _lib.check(rc, "dr_ginet_large_input_grad_pass")
 
 
 def _input_grad_layers(rq: _Request, h: BatchHandle, s, e):
@@ -235,7 +288,7 @@ def _input_grad_layers(rq: _Request, h: BatchHandle, s, e):
     rq.write_rows(s, e, g)
 
 
-def input_gradients(model, dataset, indices=None, batch_size=64, target=None, seed=None, fused=None, *, dx_out=None) -> InputGradients:
+def input_gradients(model, dataset, indices=None, batch_size=64, target=None, seed=None, fused=None, *, tiles=None, dx_out=None, _large=None) -> InputGradients:
     """``d (out . seed) / d x`` for the graphs ``indices`` of ``dataset`` (a
     ``GraphDataset`` or a ``GraphStore``; positions into it, default all), in
     that order, in batches of ``batch_size``.
@@ -250,20 +303,40 @@ def input_gradients(model, dataset, indices=None, batch_size=64, target=None, se
     ``[rows, x_stride]`` to write into (default: a new one); rows past the
     request are left alone.
 
+    ``tiles`` (default ``TILES_DEFAULT``): the route of graphs beyond one
+    workgroup's LDS.  ``False``: the layer route.  ``True``: a batch that
+    passes the tile checks — an fp32 store, ``fused`` not off, no non-finite
+    graph, at most 64 depth-0 clusters per graph, the tile plan within one
+    workgroup's LDS — runs ``dr_ginet_large_input_grad_pass`` (all of its
+    graphs together, ``path`` ``"tiles"``) when its largest graph does not fit
+    the single-workgroup pass, and that pass when it does; a batch that fails
+    the checks takes the layer route.  ``"force"``: every batch that passes the
+    checks takes the tile route (a diagnostic: the two fused routes write equal
+    bits).
+
     One ``dx`` buffer ``[rows, x_stride]`` serves the whole call: every launch
     writes its graphs' rows in place (``dr_input_grad.row_off``); the scratch
     slab and head of the training pass are allocated once.  The gradient with
     respect to ``edge_attr`` is exactly zero (module docstring) and is not
     returned."""
     _check_target("input_gradients", model, target, seed)
+    tiles = _check_tiles(tiles)
     rq = _Request("input_gradients", model, dataset, indices, batch_size, target, seed, fused, dx_out, "dx_out")
-    # each graph's first row of dx; the fused route's slab and head (the training pass's partials: scratch here), made on its first batch
-    c = SimpleNamespace(row_off=torch.from_numpy(rq.node_off[:-1].copy()).to(rq.dev) if rq.n else None, slab=None, head=None)
+    # each graph's first row of dx; the fused routes' slab and head (the training pass's partials: scratch here) and the tile route's dZ, made on their first batch
+    c = SimpleNamespace(row_off=torch.from_numpy(rq.node_off[:-1].copy()).to(rq.dev) if rq.n else None, slab=None, head=None, dz=None)
+    c.rmax = max((int(rq.node_off[e] - rq.node_off[s]) for s, e in rq.batches), default=0)
     for s, e in rq.batches:
         h = rq.handle(s, e)
+        if _large is not None:  # (the tests' knob: the plan's tile size and forms)
+            h.large_tile, h.large_halos, h.large_atomic_max = _large["tile"], _large["halos"], _large["atomic_max"]
         z = agg_x_for(ginet.SPEC, h) if rq.kernel_ok else None  # (the Z array off: the kernel's gather form, z null and zs 0)
         zs = rq.store.agg_x_stride if z is not None else 0
-        if rq.kernel_ok and not h.nonfinite and _lds("dr_ginet_input_grad_lds_bytes", h, rq.out_dim, zs) <= LDS_MAX:
+        plan = _tile_plan(rq, h) if tiles else None
+        fits = rq.kernel_ok and not h.nonfinite and _lds("dr_ginet_input_grad_lds_bytes", h, rq.out_dim, zs) <= LDS_MAX
+        if plan is not None and (tiles == "force" or not fits):
+            _input_grad_tiles(rq, c, h, plan, s, e)
+            rq.taken.add("tiles")
+        elif fits and (plan is not None or not tiles):
             _input_grad_fused(rq, c, h, s, e, z, zs)
             rq.taken.add("fused")
         else:
@@ -431,7 +504,8 @@ def integrated_gradients(model, dataset, indices=None, batch_size=64, target=Non
 
     ``model``, ``dataset``, ``indices``, ``batch_size``, ``target``, ``seed``,
     ``fused``: as :func:`input_gradients` (``"pred"`` is decided once, from the
-    forward at ``x``).  ``baseline``: ``None`` (zeros: the dataset mean of
+    forward at ``x``; there is no ``tiles`` here: graphs beyond one workgroup's
+    LDS stay on the layer route).  ``baseline``: ``None`` (zeros: the dataset mean of
     standardised features), an ``[F]`` vector given to every node, or a
     ``[rows, F]`` tensor in the request's node order (no graph may then be
     requested twice).  ``groups``: workgroups per graph of the fused pass, each

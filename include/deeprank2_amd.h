@@ -544,6 +544,44 @@ int64_t dr_ginet_large_conv_lds_bytes_bf16(int32_t n_nodes, int32_t n_feat, int3
 int64_t dr_ginet_tail_lds_bytes(int32_t k0, int32_t p1_edges, int32_t k1, int32_t transpose_aliased,
                                 int32_t out_dim);
 
+/* GINet input gradients (dr_ginet_input_grad_pass above) for graphs larger than
+ * one workgroup's LDS: what
+ *   torch.autograd.grad((model(batch) * seed).sum(), batch.x)
+ * returns, in three launches on the caller's stream and no memset:
+ *   1. dr_ginet_large_pass's tile kernel, unchanged;
+ *   2. one workgroup per graph: dr_ginet_large_pass's tail (the same
+ *      arithmetic, bit for bit), then, from the gradient dp1 reaching each
+ *      depth-0 pooling winner through relu and the winning node a1,
+ *        dZ[i, :] = sum over (k, ch) with a1[k, ch] = i of dp1[k, ch] * [W1; W1e][ch, :F]
+ *                   (channels in ascending order, one fmaf each, from +0)
+ *      into the graph's rows of dz, which the workgroup zeroes first;
+ *   3. one workgroup per tile of the plan:
+ *        dX[m, :] = sum over the transposed CSR row m (store t_rowptr / t_col: the
+ *                   original edge order) of dZ[t_col[s], :], one fp32 add at a time from +0.
+ * Graph b's node m goes to dx[(row_off[b] + m) * dx_stride ...] as 16-byte rows,
+ * zeros in columns F .. dx_stride - 1; a node without an in-edge gets exact
+ * zeros.  Deterministic: no atomics beyond the tile kernel's order-free max
+ * keys, no word written by two threads.  On graphs dr_ginet_input_grad_pass
+ * takes as well, dx, out, the slab and the head hold that entry's bits, for
+ * every tile size and either form of the plan (halos, part_key).  The gradient
+ * with respect to edge_attr is exactly zero and is not written.
+ * plan, conv_lds_bytes, tail_lds_bytes: as dr_ginet_large_pass (the tail needs
+ * no LDS beyond dr_ginet_tail_lds_bytes); the plan is left as that entry
+ * leaves it (part_key back at zero), so training passes and these may share
+ * one.  dz: [plan->z_row0[B], r4(F)] fp32 workspace, 16-byte aligned, contents
+ * undefined on entry and on exit (not plan->z: the tail reads that while dz is
+ * being formed).  pass, ig: as dr_ginet_input_grad_pass.
+ * Refused before any launch: everything dr_ginet_large_pass refuses; DR_E_ARG
+ * for a NULL ig, dx, row_off or dz, a dx or dz that is not 16-byte aligned, a
+ * dx_stride below F or not a multiple of 4, a pass without DR_PASS_BACKWARD, a
+ * non-NULL pass->slot or pass->step_counter, or a store without t_rowptr,
+ * t_col or cl0; DR_E_UNSUPPORTED for compute_dtype != DR_DTYPE_F32.  n_batch 0
+ * returns DR_OK once the arguments pass.                                      */
+int dr_ginet_large_input_grad_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                                   const dr_large_plan* plan, const dr_ginet_weights* w, const dr_pass* pass,
+                                   const dr_input_grad* ig, float* dz,
+                                   int32_t conv_lds_bytes, int32_t tail_lds_bytes, void* stream);
+
 /* ---- FoutNet (deeprank2/neuralnets/gnn/foutnet.py:72-118) ---------------- */
 
 /* FoutNet weights, all row-major as the torch parameters are stored.       */

@@ -25,6 +25,11 @@ and after).  The variants are interleaved in one process and each runs
 last lines say whether the fused route beats the layer route by more than five
 times that route's own spread (the bar for keeping it the default).
 
+``--large`` measures the tile route on atom-level graphs instead
+(``main_large``: the public call with ``tiles=True`` against the layer route,
+the parent's only route for these graphs, and the bare passes), by the same
+rules.
+
 ``--ig`` measures integrated gradients instead (``main_ig``: the bare
 ``dr_ginet_integrated_grad_pass`` for each group count, the public call, and
 the layer route as the baseline), by the same rules.
@@ -180,12 +185,112 @@ def main_ig(args):
                       "step_us": round(step_us, 2), "zb_us": round(zb_us, 2), "fused_wins": wins, "five_spreads_us": round(margin, 2)}))  # fmt: skip
 
 
+LARGE_B = 8
+LARGE_REPS = 10  # calls per timing of --large: the whole run stays well under a minute
+LARGE_BARE = 50  # launches of a bare pass per call (a timing window of 10 calls of ~50 us would measure the clock)
+
+
+def main_large(args):
+    """``--large``: input gradients of graphs beyond one workgroup's LDS,
+    BASELINE configs[3]-shape synthetic graphs (N 2 700 - 3 300, mean degree
+    16.7, 8 - 32 clusters), one batch of ``LARGE_B``.
+
+    * ``api_tiles``      ``input_gradients(model, store, batch, tiles=True)``: one
+                         ``dr_ginet_large_input_grad_pass`` (three launches);
+    * ``api_layers``     the default call: ``layered.ginet_forward`` with ``x``
+                         requiring grad, then ``torch.autograd.grad`` — the only
+                         route the parent offers these graphs: the baseline;
+    * ``pass_tiles``     the bare ``dr_ginet_large_input_grad_pass``, the handle,
+                         the plan and the buffers kept (the two bare passes:
+                         ``LARGE_BARE`` launches per call, us per launch);
+    * ``pass_large``     the bare ``dr_ginet_large_pass`` with FORWARD | BACKWARD on
+                         the same batch and plan: the difference prices the dZ
+                         epilogue and the dX kernel."""
+    dev = torch.device("cuda:0")
+    nb = LARGE_B
+    store = GraphStore(pack_graphs(records(make_graphs("atom", nb, 1000))), dev)
+    torch.manual_seed(0)
+    model = ginet.GINet(30, 1, 3).to(dev).eval()
+    idx = np.arange(nb)
+    f, xs, out_dim = store.n_feat, store.x_stride, 1
+
+    def api_tiles():
+        return attribution.input_gradients(model, store, indices=idx, batch_size=nb, tiles=True)
+
+    def api_layers():
+        return attribution.input_gradients(model, store, indices=idx, batch_size=nb)
+
+    a, b = api_tiles(), api_layers()
+    assert a.path == "tiles" and b.path == "layers"
+    scale = float(b.dx.abs().max())
+    assert torch.allclose(a.dx, b.dx, rtol=1e-4, atol=1e-6 * scale) and torch.allclose(a.out, b.out, rtol=1e-4, atol=1e-4), "the two routes agree"
+
+    h = BatchHandle(store, idx.astype(np.int32))
+    plan = h.large_plan(out_dim)
+    params = [p.detach().contiguous() for p in model.ordered_params()]
+    w = ginet.weights_c(params)
+    seed = torch.ones(nb, out_dim, device=dev)
+    out = torch.empty(nb, out_dim, device=dev)
+    slab = torch.empty(nb * ginet.slab_stride(f), device=dev)
+    head = torch.zeros(nb * ginet.head_stride(out_dim), device=dev)
+    p = make_pass(out_dim, _lib.DR_PASS_FORWARD | _lib.DR_PASS_BACKWARD, dout=seed, out=out, slab=slab, head=head)
+    rows = int(a.node_off[-1])
+    dx = torch.empty(rows, xs, device=dev)
+    dz = torch.empty(rows * (-(-f // 4) * 4), device=dev)
+    row_off = torch.from_numpy(a.node_off[:-1].copy()).to(dev)
+    ig = _lib.InputGradC()
+    ig.dx, ig.row_off, ig.dx_stride = dx.data_ptr(), row_off.data_ptr(), xs
+    lib = _lib.load()
+    stream = _lib.stream_ptr(dev)
+
+    def pass_tiles():
+        _lib.check(lib.dr_ginet_large_input_grad_pass(store.cstruct(), h.descs.data_ptr(), nb, plan.c, w, p, ig, dz.data_ptr(), plan.conv_lds, plan.tail_lds, stream), "dr_ginet_large_input_grad_pass")
+
+    def pass_large():
+        _lib.check(lib.dr_ginet_large_pass(store.cstruct(), h.descs.data_ptr(), nb, plan.c, w, p, plan.conv_lds, plan.tail_lds, stream), "dr_ginet_large_pass")
+
+    pass_tiles()
+    torch.cuda.synchronize()
+    assert torch.equal(dx[:, :f], a.dx), "the bare pass writes the public call's bits"
+
+    n, e, k0 = (v[idx] for v in store._sizes[:3])  # noqa: SLF001
+    print(f"B = {nb} atom-level graphs: N {int(n.min())}-{int(n.max())}, E {int(e.min())}-{int(e.max())}, K0 {int(k0.min())}-{int(k0.max())}; tiles of {plan.TILE} rows, {plan.n_tiles} tiles; reps {args.reps} ({args.reps * LARGE_BARE} launches of a bare pass), runs {args.runs}")
+    def many(body):
+        def run():
+            for _ in range(LARGE_BARE):
+                body()
+
+        return run
+
+    times = interleaved({"api_tiles": api_tiles, "api_layers": api_layers, "pass_tiles": many(pass_tiles), "pass_large": many(pass_large)}, args.runs, args.reps)
+    for name in ("pass_tiles", "pass_large"):
+        times[name] = [t / LARGE_BARE for t in times[name]]
+    rows_j = []
+    print(f"{'variant':>12} {'us/batch':>10} {'spread us':>10}  runs")
+    for name, ts in times.items():
+        mean, spread = float(np.mean(ts)), float(max(ts) - min(ts))
+        rows_j.append({"variant": name, "us": round(mean, 2), "spread_us": round(spread, 2), "runs_us": [round(x, 2) for x in ts]})
+        print(f"{name:>12} {mean:10.1f} {spread:10.1f}  {' '.join(f'{x:.1f}' for x in ts)}")
+    n_, o_ = times["api_tiles"], times["api_layers"]
+    margin = 5 * (max(o_) - min(o_))
+    wins = bool(np.mean(o_) - np.mean(n_) > margin)
+    print(f"api_tiles {np.mean(n_):.1f} us against api_layers {np.mean(o_):.1f} us, 5 x the baseline's spread {margin:.1f} us -> {'tiles win' if wins else 'no win'}")
+    epi = float(np.mean(times["pass_tiles"]) - np.mean(times["pass_large"]))
+    print(f"dZ epilogue + dX kernel (pass_tiles - pass_large): {epi:.2f} us per batch")
+    print(json.dumps({"bench": "attribution_large", "B": nb, "reps": args.reps, "runs": args.runs, "rows": rows_j, "tiles_win": wins, "five_spreads_us": round(margin, 2), "epilogue_us": round(epi, 2)}))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--reps", type=int, default=200, help="calls per timing (200: the layer route's timing window is over a second)")
+    ap.add_argument("--reps", type=int, default=None, help="calls per timing (default 200: the layer route's timing window is over a second; --large: 10, the layer route is slow on atom-level graphs)")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--ig", action="store_true", help="measure integrated gradients (main_ig) instead of the input gradients")
+    ap.add_argument("--large", action="store_true", help="measure the tile route on atom-level graphs (main_large)")
     args = ap.parse_args()
+    args.reps = args.reps or (LARGE_REPS if args.large else 200)
+    if args.large:
+        main_large(args)
+        return
     if args.ig:
         main_ig(args)
         return
