@@ -368,6 +368,7 @@ __device__ __forceinline__ void fout_tail(const dr_pass& p, const FoutTail t, in
       const float dlt = t.Dout[0] - y_g;
       if (p.loss_per_graph) p.loss_per_graph[b] = dlt * dlt;
       t.Dout[0] = 2.f * dlt * p.loss_scale;
+      for (int q = 1; q < OUT; ++q) t.Dout[q] = 0.f;  // the loss reads column 0 only (ginet_head.h alike)
     } else if (p.loss_kind == DR_LOSS_CE) {
       const int yi = (int)y_g;
       float mx = t.Dout[0];

@@ -656,6 +656,7 @@ __global__ void __launch_bounds__(HT) vb_head(VA a) {
       const float dl = sDout[0] - y_g;
       if (a.p.loss_per_graph) a.p.loss_per_graph[row] = dl * dl;
       sDout[0] = 2.f * dl * a.p.loss_scale;
+      for (int q = 1; q < OUT; ++q) sDout[q] = 0.f;  // the loss reads column 0 only (ginet_head.h alike)
     } else if (a.p.loss_kind == DR_LOSS_CE) {
       const int yi = (int)y_g;
       float mx = sDout[0];

@@ -908,6 +908,7 @@ __global__ void __launch_bounds__(NT) vanilla_graph_kernel(VGArgs a) {
       const float dl = sdout[0] - y_g;
       if (p.loss_per_graph && lead) p.loss_per_graph[row] = dl * dl;
       sdout[0] = 2.f * dl * p.loss_scale;
+      for (int q = 1; q < OUT; ++q) sdout[q] = 0.f;  // the loss reads column 0 only (ginet_head.h alike)
     } else if (p.loss_kind == DR_LOSS_CE) {
       const int yi = (int)y_g;
       float mx = sdout[0];

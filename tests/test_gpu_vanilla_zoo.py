@@ -60,25 +60,14 @@ import torch
 from _util import assert_same, dwc_mask
 
 import vanilla_zoo as V
+from vanilla_zoo import handle as _handle
+from vanilla_zoo import train_step as _train_step
 from deeprank2_amd import _lib
-from deeprank2_amd.engine import FusedTrainStep
-from deeprank2_amd.fused import LDS_MAX, BatchHandle
+from deeprank2_amd.fused import LDS_MAX
 from deeprank2_amd.neuralnets.gnn import vanilla_gnn as amd
-from deeprank2_amd.store import GraphStore
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def _handle(name, loss="mse", **knobs):
-    p = V.packed(name)
-    store = GraphStore(p, DEV)
-    if loss == "ce":
-        store.set_targets(np.arange(p.n_graphs) % 3)
-    h = BatchHandle(store, np.arange(p.n_graphs))
-    for k, v in knobs.items():
-        setattr(h, k, v)
-    return h
 
 
 def _assert_path(name, h):
@@ -100,32 +89,6 @@ def _assert_path(name, h):
     took = "chunk" if chunk else ("tiled" if planned and fe <= 4 else "untiled")  # noqa: PLR2004
     assert took == want, (took, want)
     return took
-
-
-def _train_step(name, loss, pipeline=True, **knobs):
-    """One FusedTrainStep.step of the batch under the handle knobs: outputs,
-    loss, gradients and the Adam update against the float64 oracle."""
-    f, fe, _ = V.BATCHES[name]
-    state, out_o, loss_o, _ = V.oracle(name, loss, "f64")
-    h = _handle(name, loss, **knobs)
-    if pipeline:
-        h.vanilla_pipeline = True
-    model = amd.VanillaNetwork(f, out_o.shape[1], fe)
-    model.load_state_dict(state)
-    step = FusedTrainStep(model.to(DEV).train(), loss=loss)
-    before = [p.detach().clone() for p in step.params]
-    loss_v, out = step.step(h)
-    torch.cuda.synchronize()
-    np.testing.assert_allclose(out.cpu().numpy().astype(np.float64), out_o, **V.OUT_TOL)
-    assert float(loss_v) == pytest.approx(loss_o, rel=V.LOSS_RTOL)
-    V.assert_grads_close({n: g.cpu().numpy() for n, g in zip(amd.PARAM_NAMES, step.grads)}, name, loss)
-    ref = [torch.nn.Parameter(b) for b in before]
-    for r, g in zip(ref, step.grads):
-        r.grad = g.detach().clone()
-    torch.optim.Adam(ref, lr=1e-3, weight_decay=1e-5).step()
-    for n, r, p in zip(amd.PARAM_NAMES, ref, step.params):
-        np.testing.assert_allclose(p.detach().cpu().numpy(), r.detach().cpu().numpy(), rtol=1e-5, atol=1e-7, err_msg=n)
-    return h
 
 
 # --------------------------------------------------------------------------

@@ -21,6 +21,20 @@ batch of ``vanilla_zoo.BATCHES``:
 * the float32 oracle meets the project's tolerances against the float64
   oracle on every batch and loss, no entry left out (no ReLU gate of these
   batches sits within float32 rounding of zero in a way that shows).
+
+For the per-graph kernel's cases (tests/test_gpu_vanilla_per_graph_widths.py,
+tests/test_gpu_multi_output_mse.py):
+
+* every width of ``PER_GRAPH_WIDTHS`` fits ``vanilla_graph_kernel`` by its own
+  carve, its store has x rows of r4(F) floats and, at Fe = 0, no
+  edge-attribute array; together the widths take every value of the layout
+  quantities the kernel derives from F and Fe;
+* every parameter's gradient is live at every width (F = 1 under the common
+  seed is not: ``vanilla_zoo.SEEDS``);
+* ``deg17_2`` leaves siblings of a split graph without rows, by the kernel's
+  row split restated;
+* the float32 oracle meets the same tolerances with 16 classes and with MSE
+  over 3 and 16 outputs, whose last-layer rows from 1 on are exactly zero.
 """
 
 from __future__ import annotations
@@ -154,3 +168,145 @@ def test_float32_oracle_meets_the_tolerances(name, loss):
         np.testing.assert_allclose(g32[n], g64[n], rtol=V.GRAD_RTOL, atol=floor, err_msg=n)
         atol, dev = V.grad_atol(g64[n], g32[n])
         assert floor <= atol <= max(floor, V.GRAD_CEILING * float(np.abs(g64[n]).max())) and atol <= max(floor, 4.0 * dev)
+
+
+# --------------------------------------------------------------------------
+# the per-graph kernel's widths (test_gpu_vanilla_per_graph_widths.py)
+# --------------------------------------------------------------------------
+
+PER_GRAPH = [f"w{f}_{fe}" for f, fe in V.PER_GRAPH_WIDTHS]
+# (name, loss, out_dim) beyond one output and three classes, on the GPU in
+# test_gpu_vanilla_per_graph_widths.py and test_gpu_multi_output_mse.py
+MULTI_OUT = [(n, "ce", 16) for n in V.CE16] + [(n, "mse", out) for n, out in V.MSE_MULTI]
+
+
+def _r4(v):
+    return (v + 3) & ~3
+
+
+@pytest.mark.parametrize("name", PER_GRAPH)
+def test_per_graph_widths_fit_the_kernel_and_stores_are_as_claimed(name):
+    """Every width of ``PER_GRAPH_WIDTHS`` runs on vanilla_graph_kernel: the
+    largest graph's carve (dr_vanilla_fused_lds_bytes, a host function) is
+    within 160 KiB, the device layout's x rows are r4(F) floats, and a store
+    with Fe = 0 carries no edge-attribute array."""
+    from deeprank2_amd import _lib
+    from deeprank2_amd.fused import BatchHandle
+    from deeprank2_amd.neuralnets.gnn import vanilla_gnn as amd
+    from deeprank2_amd.store import GraphStore
+
+    f, fe, _ = V.BATCHES[name]
+    assert (f, fe) in V.PER_GRAPH_WIDTHS and 1 <= f <= 32 and 0 <= fe <= amd.FUSED_MAX_FE  # noqa: PLR2004
+    p = V.packed(name)
+    n, e = (int(a.max()) for a in p.sizes()[:2])
+    assert n == 130 and p.n_graphs == 4  # noqa: PLR2004
+    assert int(_lib.load().dr_vanilla_fused_lds_bytes(n, e, fe)) <= LDS_MAX
+    store = GraphStore(p, "cpu")
+    assert store.n_feat == f and store.x_stride == _r4(f) and tuple(store.x.shape) == (int(p.sizes()[0].sum()), _r4(f))
+    assert not store.x[:, f:].any()  # zero pad columns
+    assert store.n_edge_feat == fe and (p.edge_attr is None) == (store.edge_attr is None) == (fe == 0)
+    h = BatchHandle(store, np.arange(p.n_graphs))
+    for k in (None, 1, 2, 3, 4):
+        h.vanilla_split = k
+        assert amd.fused_fits(h, f, fe) and (k is None or amd.split_k(h, f, fe) == k)
+    h.vanilla_pipeline = True
+    assert not amd.fused_fits(h, f, fe) and amd.split_k(h, f, fe) == 1
+
+
+def test_per_graph_widths_take_every_layout_value():
+    """What vanilla_graph.hip derives from F and Fe, over ``PER_GRAPH_WIDTHS``:
+    the x row stride, the 16-row and 16-column tile counts of its
+    weight-gradient GEMMs (M = F, Nn = F + 33), both states of the packed
+    row-pass block's upper half (k = 16 + blk < F), every FE instantiation."""
+    fs = {f for f, _ in V.PER_GRAPH_WIDTHS}
+    assert {_r4(f) for f in fs} >= {4, 12, 16, 20, 32}
+    assert {(f + 15) // 16 for f in fs} == {1, 2} and {15, 16, 17} <= fs
+    assert {f + 33 for f in fs} >= {34, 48, 49, 64, 65} and {(f + 33 + 15) // 16 for f in fs} == {3, 4, 5}
+    assert {1, 32} <= fs  # every clamp at 0; no pad column
+    assert {f > 16 for f in fs} == {True, False} and {16, 17} <= fs
+    assert {fe for _, fe in V.PER_GRAPH_WIDTHS} == {0, 1, 2, 3, 4}
+    assert min(f for f, fe in V.PER_GRAPH_WIDTHS if fe == 4) == 12 and (1, 0) in V.PER_GRAPH_WIDTHS  # noqa: PLR2004
+    assert not set(V.PER_GRAPH_ONLY) & {(f, fe) for f in V.CHUNK_F for fe in V.CHUNK_FE}
+
+
+@pytest.mark.parametrize("name", PER_GRAPH)
+def test_every_gradient_is_live_at_the_per_graph_widths(name):
+    """A narrow model can be dead (at F = 1 one ReLU decides a layer): every
+    parameter's gradient has non-zero entries, and so has every column block of
+    the edge-MLP weights (Wa, Wb, and Wc where Fe > 0) in both layers."""
+    f, fe, _ = V.BATCHES[name]
+    g = V.oracle(name, "mse", "f64")[3]
+    for n in PARAM_NAMES:
+        assert np.any(g[n]), n
+    for layer in (1, 2):
+        we = g[f"_external{layer}._edge_mlp.0.weight"]
+        assert we.shape == (32, 2 * f + fe)
+        assert np.any(we[:, :f]) and np.any(we[:, f : 2 * f]) and (fe == 0 or np.any(we[:, 2 * f :]))
+        wn = g[f"_external{layer}._node_mlp.0.weight"]
+        assert np.any(wn[:, :f]) and np.any(wn[:, f:])
+
+
+@pytest.mark.parametrize(("name", "loss", "out_dim"), MULTI_OUT)
+def test_float32_oracle_meets_the_tolerances_with_several_outputs(name, loss, out_dim):
+    """``test_float32_oracle_meets_the_tolerances`` for the cases with 16
+    classes and with MSE over several outputs; and the multi-output MSE rule:
+    the last layer's rows and bias entries from 1 on get exactly zero."""
+    _, out64, loss64, g64 = V.oracle(name, loss, "f64", out_dim)
+    _, out32, loss32, g32 = V.oracle(name, loss, "f32", out_dim)
+    assert out64.shape == (len(V.datas(name)), out_dim)
+    np.testing.assert_allclose(out32, out64, **V.OUT_TOL)
+    assert loss32 == pytest.approx(loss64, rel=V.LOSS_RTOL)
+    for n in PARAM_NAMES:
+        floor = max(1e-6, V.GRAD_NTOL * float(np.abs(g64[n]).max()))
+        np.testing.assert_allclose(g32[n], g64[n], rtol=V.GRAD_RTOL, atol=floor, err_msg=n)
+        atol, dev = V.grad_atol(g64[n], g32[n])
+        assert floor <= atol <= max(floor, V.GRAD_CEILING * float(np.abs(g64[n]).max())) and atol <= max(floor, 4.0 * dev)
+        assert np.any(g64[n]), n
+    w, b = g64["_graph_mlp.2.weight"], g64["_graph_mlp.2.bias"]
+    if loss == "mse":
+        for g in (g64, g32):
+            assert not np.any(g["_graph_mlp.2.weight"][1:]) and not np.any(g["_graph_mlp.2.bias"][1:])
+        assert np.any(w[0]) and b[0] != 0
+        y = np.array([float(d.y) for d in V.datas(name)])
+        assert loss64 == pytest.approx(float(((out64[:, 0] - y) ** 2).sum() / (len(y) * out_dim)), rel=1e-12)
+    else:  # every class has a logit gradient of its own
+        assert np.abs(w).max(axis=1).min() > 0 and np.all(b != 0)
+
+
+def _row_bound(rp, n, r, k, rw=16):
+    """vanilla_graph.hip's ``row_bound`` restated: the first row i with
+    rp[i] + RW i >= ceil(r (E + RW N) / k)."""
+    if r <= 0:
+        return 0
+    if r >= k:
+        return n
+    t = ((int(rp[n]) + rw * n) * r + k - 1) // k
+    return next((i for i in range(n) if int(rp[i]) + rw * i >= t), n)
+
+
+def test_deg17_2_leaves_siblings_without_rows():
+    """The degenerate batch at (17, 2) is the graphs of ``deg`` (same tiles),
+    and under the kernel's edge-balanced row split its one-node graph gives
+    k - 1 siblings no row at every k > 1 (the two-node graph: k - 2), while
+    every graph of the ``w`` batches gives every sibling rows."""
+    f, fe, _ = V.BATCHES["deg17_2"]
+    p, q = V.packed("deg17_2"), V.packed("deg")
+    assert (f, fe) == (17, 2) and p.n_feat == 17 and p.edge_attr.shape[1] == 2  # noqa: PLR2004
+    np.testing.assert_array_equal(p.rowptr, q.rowptr)
+    np.testing.assert_array_equal(p.col, q.col)
+    np.testing.assert_array_equal(p.x, q.x[:, :17])
+
+    def empty_siblings(pk, k):
+        out = []
+        for g, n in enumerate(int(v) for v in pk.sizes()[0]):
+            n0 = int(pk.node_off[g])
+            rp = pk.rowptr[n0 + g : n0 + g + n + 1]
+            b = [_row_bound(rp, n, r, k) for r in range(k + 1)]
+            assert b[0] == 0 and b[-1] == n and all(x <= y for x, y in zip(b, b[1:]))
+            out.append(sum(x == y for x, y in zip(b, b[1:])))
+        return out
+
+    for k in (2, 3, 4):
+        e = empty_siblings(p, k)
+        assert e[0] == k - 1 and e[1] == k - 2 and [int(v) for v in p.sizes()[0][:2]] == [1, 2]
+        assert not any(empty_siblings(V.packed("w17_2"), k))

@@ -3,7 +3,9 @@ the host test (test_vanilla_zoo_host.py) and the GPU test
 (test_gpu_vanilla_zoo.py) both need of them: the packed arrays, the pipeline's
 tile plan built on the CPU, the host carve sizes with the dispatch rule of
 ``chunk_fused()`` restated, the oracle in float64 and float32, the tolerance
-rule, and a float64 restatement of the network on the packed and planned
+rule, one training step on the GPU held to them (``train_step``, shared with
+test_gpu_vanilla_per_graph_widths.py and test_gpu_multi_output_mse.py), and a
+float64 restatement of the network on the packed and planned
 arrays (the form the kernels compute, so that a ``col`` for ``t_col`` mix-up
 can be put into it).
 """
@@ -27,11 +29,32 @@ CHUNK = 64
 CHUNK_F = (12, 29, 32)  # widths on the chunk-fused path ...
 CHUNK_FE = (0, 1, 4)
 UNFUSED_WIDTHS = ((40, 3), (64, 8), (30, 5))  # ... and beyond it (F > 32 or Fe > 4)
+# Widths run on the per-graph kernel alone (vanilla_graph_kernel<FE>,
+# test_gpu_vanilla_per_graph_widths.py), outside CHUNK_F x CHUNK_FE: F = 1 (every
+# min(.., M - 1) / min(.., Nn - 1) clamp of its GEMMs at 0), F = 4 (x_stride 4),
+# F = 15 | 16 (F + 33 = 48 | 49: three | four column tiles of the weight-gradient
+# GEMMs; at 16 the upper half of the packed row-pass block is all zero), F = 17
+# (its first live row, two row tiles, x_stride 20), F = 31 (F + 33 = 64) and
+# F = 32 (five column tiles, no pad column), over every FE instantiation.
+PER_GRAPH_ONLY = ((1, 0), (1, 3), (4, 2), (15, 1), (16, 4), (17, 2), (31, 3), (32, 2))
+PER_GRAPH_WIDTHS = tuple((f, fe) for f in CHUNK_F for fe in CHUNK_FE) + PER_GRAPH_ONLY
+# Seed of the oracle's weights where 11, every other batch's, leaves a narrow
+# model dead: at (1, 3) the one node channel's ReLU is off on every node, so
+# all eight layer gradients are exactly zero, and at (4, 2) one channel of four
+# is live.  The first seeds after 11 with every node channel of layer 2 live
+# (test_vanilla_zoo_host.py holds every width to a live gradient per parameter).
+SEEDS = {"w1_3": 30, "w4_2": 13}
+# Beyond one output and three classes: cross entropy over 16 (= DR_MAX_OUT)
+# classes, and (name, out_dim) of the MSE cases with several outputs
+CE16 = ("w12_0", "w32_4")
+MSE_MULTI = (("asym", 3), ("w12_0", 16))
 
 # name -> (F, Fe, builder of the graphs)
 BATCHES = {
     "asym": (30, 3, lambda: graph_zoo.without_clusters(graph_zoo.asymmetric(**graph_zoo.ASYM_BATCH))),
     "deg": (30, 3, lambda: graph_zoo.without_clusters(graph_zoo.degenerate())),
+    # the degenerate batch at F = 17, Fe = 2, for the per-graph kernel (its one- and two-node graphs leave siblings of a split without a row)
+    "deg17_2": (17, 2, lambda: graph_zoo.without_clusters(graph_zoo.resized(graph_zoo.degenerate(fe=2), 17, 2))),
     "dense3": (30, 3, lambda: graph_zoo.between_small(graph_zoo.dense_tiles(3), 3)),
     "dense4": (30, 4, lambda: graph_zoo.between_small(graph_zoo.dense_tiles(4), 4)),
     "hub_tiled": (30, 3, lambda: graph_zoo.between_small(graph_zoo.hub(graph_zoo.HUB_TILED, y=HUB_Y[0]))),
@@ -46,7 +69,7 @@ BATCHES = {
 # is still checked to the same relative precision (test_vanilla_zoo_host.py
 # asserts both).
 HUB_Y = (-1.0, -0.8)
-for _f, _fe in [(f, fe) for f in CHUNK_F for fe in CHUNK_FE] + list(UNFUSED_WIDTHS):
+for _f, _fe in [(f, fe) for f in CHUNK_F for fe in CHUNK_FE] + list(UNFUSED_WIDTHS) + list(PER_GRAPH_ONLY):
     BATCHES[f"w{_f}_{_fe}"] = (_f, _fe, functools.partial(graph_zoo.widths, _f, _fe))
 HARD = {"dense3": 2, "dense4": 2, "hub_tiled": 2, "hub_untiled": 2}  # position of the hard graph (between_small)
 WIDTH_BATCHES = tuple(n for n in BATCHES if n.startswith("w"))
@@ -57,13 +80,16 @@ LOSSES = {**{n: ("mse",) for n in BATCHES}, "asym": ("mse", "ce"), "deg": ("mse"
 STATS = {
     "asym": (9, 67, 401, 392),
     "deg": (19, 71, 449, 449),
+    "deg17_2": (19, 71, 449, 449),
     "dense3": (11, 399, 2561, 2976),
     "dense4": (11, 399, 2561, 2976),
     "hub_tiled": (20, 1001, 1001, 339),
     "hub_untiled": (23, 1201, 1201, 339),  # (what the plan would be: it is refused)
     **{n: (6, 108, 369, 432) for n in WIDTH_BATCHES},
 }
-# ... and the kernels the default knobs then run (``expected_path``)
+# ... and the kernels the pipeline then runs under its default knobs
+# (``expected_path``; the PER_GRAPH_ONLY widths are within the chunk kernels'
+# limits too, and only the per-graph test runs them on the GPU)
 PATHS = {
     **{n: "chunk" for n in BATCHES},
     "hub_tiled": "tiled",
@@ -164,14 +190,20 @@ def expected_path(f, fe, words, tile_rows, stats):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle(name, loss="mse", dtype="f64"):
+def oracle(name, loss="mse", dtype="f64", out_dim=None):
     """One forward + backward of ``oracle.gnn_ref.VanillaNetwork`` in float64
     or float32 from the same float32 initial weights and inputs: (state dict,
     outputs, loss, gradients by parameter name).  ``loss``: "mse" on the stored
-    targets (1 output) or "ce" over 3 classes (targets i % 3)."""
+    targets (1 output) or "ce" over 3 classes (targets i % 3).  ``out_dim``
+    overrides the output count: "ce" then runs over that many classes (targets
+    i % out_dim), and "mse" with more than one output is the project's
+    multi-output rule restated from ``engine._layered_step`` and
+    ``engine.loss_scale``: column 0 alone against the stored targets, summed
+    and divided by B * out_dim."""
     f, fe, _ = BATCHES[name]
-    out_dim = 1 if loss == "mse" else 3
-    torch.manual_seed(11)
+    if out_dim is None:
+        out_dim = 1 if loss == "mse" else 3
+    torch.manual_seed(SEEDS.get(name, 11))
     model = gnn_ref.VanillaNetwork(f, out_dim, fe)
     state = {k: v.detach().clone() for k, v in model.state_dict().items()}
     bat = graph_zoo.batch(datas(name))
@@ -180,10 +212,12 @@ def oracle(name, loss="mse", dtype="f64"):
         model = model.double()
         bat.x, bat.edge_attr, y = bat.x.double(), bat.edge_attr.double(), y.double()
     out = model(bat)
-    if loss == "mse":
+    if loss == "mse" and out_dim == 1:
         lval = torch.nn.functional.mse_loss(out.reshape(-1), y)
+    elif loss == "mse":
+        lval = ((out[:, 0] - y) ** 2).sum() / (len(datas(name)) * out_dim)
     else:
-        lval = torch.nn.functional.cross_entropy(out, torch.arange(len(datas(name))) % 3)
+        lval = torch.nn.functional.cross_entropy(out, torch.arange(len(datas(name))) % out_dim)
     lval.backward()
     grads = {n: p.grad.detach().numpy().copy() for n, p in model.named_parameters()}
     return state, out.detach().numpy(), float(lval.detach()), grads
@@ -207,11 +241,11 @@ def grad_atol(ref64, ref32):
     return max(base, min(4.0 * dev, GRAD_CEILING * scale)), dev
 
 
-def assert_grads_close(grads, name, loss):
+def assert_grads_close(grads, name, loss, out_dim=None):
     """``grads`` (by parameter name) against the float64 oracle under
     ``grad_atol``; a failure lists the oracle's and the kernel's deviation of
     every parameter."""
-    g64, g32 = oracle(name, loss, "f64")[3], oracle(name, loss, "f32")[3]
+    g64, g32 = oracle(name, loss, "f64", out_dim)[3], oracle(name, loss, "f32", out_dim)[3]
     lines, bad = [], []
     for n in PARAM_NAMES:
         got = np.asarray(grads[n], dtype=np.float64)
@@ -222,6 +256,62 @@ def assert_grads_close(grads, name, loss):
             bad.append(n)
     print("\n".join(lines))
     assert not bad, f"{name}/{loss}: {bad} outside tolerance\n" + "\n".join(lines)
+
+
+# --------------------------------------------------------------------------
+# one training step on the GPU against the oracle
+# --------------------------------------------------------------------------
+
+DEV = "cuda:0"
+
+
+def handle(name, loss="mse", out_dim=None, **knobs):
+    """A batch handle of the whole batch on a fresh GPU store ("ce": targets
+    i % out_dim, 3 classes by default) with the knobs set."""
+    p = packed(name)
+    store = GraphStore(p, DEV)
+    if loss == "ce":
+        store.set_targets(np.arange(p.n_graphs) % (3 if out_dim is None else out_dim))
+    h = BatchHandle(store, np.arange(p.n_graphs))
+    for k, v in knobs.items():
+        setattr(h, k, v)
+    return h
+
+
+def train_step(name, loss, pipeline=True, out_dim=None, got=None, **knobs):
+    """One FusedTrainStep.step of the batch under the handle knobs: outputs,
+    loss, gradients and the Adam update against the float64 oracle
+    (``out_dim``: as ``oracle``).  ``got``: a dict that receives the step's
+    "out", "loss" and "grads" (by parameter name) as numpy copies."""
+    import pytest  # noqa: PLC0415
+
+    from deeprank2_amd.engine import FusedTrainStep  # noqa: PLC0415
+    from deeprank2_amd.neuralnets.gnn import vanilla_gnn as amd  # noqa: PLC0415
+
+    f, fe, _ = BATCHES[name]
+    state, out_o, loss_o, _ = oracle(name, loss, "f64", out_dim)
+    h = handle(name, loss, out_dim, **knobs)
+    if pipeline:
+        h.vanilla_pipeline = True
+    model = amd.VanillaNetwork(f, out_o.shape[1], fe)
+    model.load_state_dict(state)
+    step = FusedTrainStep(model.to(DEV).train(), loss=loss)
+    before = [p.detach().clone() for p in step.params]
+    loss_v, out = step.step(h)
+    torch.cuda.synchronize()
+    grads = {n: g.cpu().numpy() for n, g in zip(PARAM_NAMES, step.grads)}
+    if got is not None:
+        got.update(out=out.cpu().numpy().copy(), loss=float(loss_v), grads={n: g.copy() for n, g in grads.items()})
+    np.testing.assert_allclose(out.cpu().numpy().astype(np.float64), out_o, **OUT_TOL)
+    assert float(loss_v) == pytest.approx(loss_o, rel=LOSS_RTOL)
+    assert_grads_close(grads, name, loss, out_dim)
+    ref = [torch.nn.Parameter(b) for b in before]
+    for r, g in zip(ref, step.grads):
+        r.grad = g.detach().clone()
+    torch.optim.Adam(ref, lr=1e-3, weight_decay=1e-5).step()
+    for n, r, p in zip(PARAM_NAMES, ref, step.params):
+        np.testing.assert_allclose(p.detach().cpu().numpy(), r.detach().cpu().numpy(), rtol=1e-5, atol=1e-7, err_msg=n)
+    return h
 
 
 # --------------------------------------------------------------------------

@@ -16,7 +16,10 @@ r4(F) <= 32 down the FoutNet / SGAT kernel's branch without the fused front
 are sized by K0 too).
 
 Loss: MSE on the stored targets for OUT = 1, else cross entropy with targets
-``i % OUT``.
+``i % OUT``.  ``loss="mse"`` overrides that for OUT > 1 (test_gpu_multi_output_mse.py):
+the stored targets are kept and the loss is the project's multi-output
+regression rule, restated from ``engine._layered_step`` and
+``engine.loss_scale``: ``((out[:, 0] - y) ** 2).sum() / (B * OUT)``.
 """
 
 from __future__ import annotations
@@ -43,6 +46,14 @@ WIDTHS = {
     "sgat": FOUT_WIDTHS,
     "nocluster": ((1, 1), (16, 16), (32, 1), (33, 5), (64, 16)),
     "ginet": ((1, 1), (32, 16), (33, 1), (64, 16)),
+}
+# (F, OUT) of the MSE cases with several outputs (``loss="mse"``): three at the
+# batch's own width, 16 (= DR_MAX_OUT) at a width the family already runs
+MSE_MULTI = {
+    "foutnet": ((30, 3), (33, 16)),
+    "sgat": ((30, 3), (33, 16)),
+    "nocluster": ((30, 3), (32, 16)),
+    "ginet": ((30, 3), (32, 16)),
 }
 K0_OVER_64 = (8, 16)  # (F, OUT) of the k0_over_64 batch
 K0_FAMILIES = ("foutnet", "sgat", "ginet")
@@ -71,14 +82,14 @@ def ring70():
     return graph_zoo._graph(np.random.default_rng(5), 70, np.stack([i, (i + 1) % 70], 1), i, i % 5, "ring70", directed=np.stack([i, (i + 7) % 70], 1))  # noqa: SLF001
 
 
-def datas(family, f, out, batch="asym"):
+def datas(family, f, out, batch="asym", loss=None):
     """The graphs of one case, built once per process and left unchanged
     (collate copies of them with ``graph_zoo.batch``)."""
-    return _datas(family, f, out, batch)
+    return _datas(family, f, out, batch, loss)
 
 
 @functools.lru_cache(maxsize=None)
-def _datas(family, f, out, batch):
+def _datas(family, f, out, batch, loss):
     fe = FAMILIES[family][1]
     ds = graph_zoo.asymmetric(fe=fe, **graph_zoo.ASYM_BATCH)
     if batch == "k0_over_64":
@@ -90,24 +101,26 @@ def _datas(family, f, out, batch):
     for i, d in enumerate(ds):
         if family == "sgat":
             d.edge_attr = d.edge_attr * SGAT_EDGE_SCALE
-        if out > 1:
+        if out > 1 and loss != "mse":
             d.y = torch.tensor([float(i % out)])
     return tuple(ds)
 
 
-def oracle(family, f, out, batch="asym", dtype=torch.float64):
+def oracle(family, f, out, batch="asym", dtype=torch.float64, loss=None):
     """One training-mode forward + backward of the oracle in ``dtype``:
     ``{"state", "mask", "out", "loss", "grads"}``.  The weights are drawn in
     fp32 under seed 11 (``state``: what the HIP model loads) and the dropout
     mask in fp32 under seed 3 (``torch.rand`` depends on the default dtype),
-    whatever ``dtype`` the step then runs in.  Cached per case and dtype."""
-    return _oracle(family, f, out, batch, dtype)
+    whatever ``dtype`` the step then runs in.  Cached per case, dtype and loss
+    override."""
+    return _oracle(family, f, out, batch, dtype, loss)
 
 
 @functools.lru_cache(maxsize=None)
-def _oracle(family, f, out, batch, dtype):
+def _oracle(family, f, out, batch, dtype, loss):
+    assert loss in (None, "mse")
     cls, fe, has_drop = FAMILIES[family]
-    ds = datas(family, f, out, batch)
+    ds = datas(family, f, out, batch, loss)
     assert torch.get_default_dtype() == torch.float32
     torch.manual_seed(11)
     model = cls(f, out, fe).train()
@@ -124,7 +137,12 @@ def _oracle(family, f, out, batch, dtype):
             setattr(bat, k, getattr(bat, k).to(dtype))
         y = bat.y.clone()
         res = model(bat)
-        lval = torch.nn.functional.mse_loss(res.reshape(-1), y) if out == 1 else torch.nn.functional.cross_entropy(res, y.long())
+        if out == 1:
+            lval = torch.nn.functional.mse_loss(res.reshape(-1), y)
+        elif loss == "mse":  # column 0 alone, 1 / (B * OUT)
+            lval = ((res[:, 0] - y) ** 2).sum() / (len(ds) * out)
+        else:
+            lval = torch.nn.functional.cross_entropy(res, y.long())
         lval.backward()
     finally:
         torch.set_default_dtype(torch.float32)
@@ -134,18 +152,19 @@ def _oracle(family, f, out, batch, dtype):
 
 
 @functools.lru_cache(maxsize=None)
-def packed(family, f, out, batch="asym"):
+def packed(family, f, out, batch="asym", loss=None):
     """The case's graphs in the store layout (host side; shared, unchanged)."""
     from deeprank2_amd.store import pack_graphs, records_from_batch  # noqa: PLC0415
 
-    return pack_graphs(records_from_batch(graph_zoo.batch(datas(family, f, out, batch))), require_clusters=family != "nocluster")
+    return pack_graphs(records_from_batch(graph_zoo.batch(datas(family, f, out, batch, loss))), require_clusters=family != "nocluster")
 
 
-def case(family, f, out, batch="asym"):
+def case(family, f, out, batch="asym", loss=None):
     """The inputs and the fp64 reference of one GPU case (cached, shared,
     never modified): ``datas``, ``f``, ``out_dim``, ``loss_kind`` ("mse" /
-    "ce"), and ``oracle``'s record."""
-    return {"datas": datas(family, f, out, batch), "f": f, "out_dim": out, "loss_kind": "mse" if out == 1 else "ce", **oracle(family, f, out, batch)}
+    "ce"; ``loss`` overrides the choice by ``out``), and ``oracle``'s record."""
+    kind = loss or ("mse" if out == 1 else "ce")
+    return {"datas": datas(family, f, out, batch, loss), "f": f, "out_dim": out, "loss_kind": kind, **oracle(family, f, out, batch, loss=loss)}
 
 
 def all_cases():
