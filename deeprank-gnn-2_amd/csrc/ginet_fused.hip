@@ -1851,7 +1851,13 @@ __device__ __forceinline__ void tile_partial_max(const dr_large_plan& pl, const 
 
 // One tile of TR nodes: Z rows (CSR gather over HBM/L2), H = relu(Z W^T) on
 // MFMA, and the tile's partial depth-0 max per (cluster, channel).
-__device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
+// IG (dr_ginet_large_integrated_grad_pass): every gathered chunk is rescaled to
+// Zb + alpha (Z - Zb) before it is stored to sZ, with graph_body<..., IG>'s
+// expressions (zb: the store-wide A xb, rows of zb_stride words, or NULL: alpha Z),
+// over columns 0 .. r4(F) - 1: all the MFMA and the tail read but zeros.
+template <bool IG = false>
+__device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds, float ig_alpha = 0.f,
+                                              const float* ig_zb = nullptr, int ig_zb_stride = 0) {
   const GinetArgs& a = la.g;
   const dr_large_plan& pl = la.plan;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1889,7 +1895,21 @@ __device__ __forceinline__ void conv_tile_f32(const LargeArgs& la, float* lds) {
       const int eb = rowp[r] - ebase, ee = rowp[r + 1] - ebase;
       for (int ch = sub; ch < nch; ch += 8) {
         const int c4 = ch * 4;
-        const float4 acc = gather_row_chunk(col, eb, ee, Xs, XS, c4);  // (the _imm form measured +0.4 us on the halo path)
+        float4 acc = gather_row_chunk(col, eb, ee, Xs, XS, c4);  // (the _imm form measured +0.4 us on the halo path)
+        if (IG) {
+          if (ig_zb) {
+            const float4 zb = *reinterpret_cast<const float4*>(ig_zb + (n0 + r0 + r) * (int64_t)ig_zb_stride + c4);
+            acc.x = fmaf(ig_alpha, acc.x - zb.x, zb.x);
+            acc.y = fmaf(ig_alpha, acc.y - zb.y, zb.y);
+            acc.z = fmaf(ig_alpha, acc.z - zb.z, zb.z);
+            acc.w = fmaf(ig_alpha, acc.w - zb.w, zb.w);
+          } else {
+            acc.x *= ig_alpha;
+            acc.y *= ig_alpha;
+            acc.z *= ig_alpha;
+            acc.w *= ig_alpha;
+          }
+        }
         float* zr = sZ + r * LDW + c4;
         zr[0] = acc.x;
         zr[1] = acc.y;
@@ -2312,24 +2332,128 @@ __global__ void __launch_bounds__(NT) ginet_large_input_grad_tail_kernel(LargeAr
 // for the rows of one tile: 8 lanes per row, one 16-byte chunk each, dz read
 // from global memory (a graph's block stays in its tiles' L2: tile_ctx);
 // zeros past r4(F).
-__global__ void __launch_bounds__(NTA) ginet_large_dx_kernel(LargeArgs la, dr_input_grad ig, const float* dz) {
-  const dr_graph_store& s = la.g.s;
-  const TileCtx x = tile_ctx(la.g.descs, la.plan);
+// (dz: the first dz row of the tile's graph; out: the tile's first output row, rows of dx_stride words)
+__device__ __forceinline__ void dx_tile_rows(const dr_graph_store& s, const TileCtx& x, const float* dzg, float* out,
+                                             int dx_stride) {
   const int tid = threadIdx.x, DS = r4(s.n_feat);
   const int* trp = s.t_rowptr + x.d.node0 + x.d.gid + x.r0;
   const uint16_t* tcol = s.t_col + x.d.col0;
-  const float* dzg = dz + (int64_t)la.plan.z_row0[x.b] * DS;
-  float* out = ig.dx + (ig.row_off[x.b] + x.r0) * (int64_t)ig.dx_stride;
-  const int sub = tid & 7, nchd = DS >> 2, ncho = ig.dx_stride >> 2;
+  const int sub = tid & 7, nchd = DS >> 2, ncho = dx_stride >> 2;
   for (int r = tid >> 3; r < x.nrows; r += NTA / 8) {
     const int eb = trp[r], ee = trp[r + 1];
-    float* row = out + r * (int64_t)ig.dx_stride;
+    float* row = out + r * (int64_t)dx_stride;
     for (int ch = sub; ch < ncho; ch += 8) {
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
       if (ch < nchd) acc = drk::gather_row_chunk(tcol, eb, ee, dzg, DS, ch * 4);
       *reinterpret_cast<float4*>(row + ch * 4) = acc;
     }
   }
+}
+
+__global__ void __launch_bounds__(NTA) ginet_large_dx_kernel(LargeArgs la, dr_input_grad ig, const float* dz) {
+  const TileCtx x = tile_ctx(la.g.descs, la.plan);
+  dx_tile_rows(la.g.s, x, dz + (int64_t)la.plan.z_row0[x.b] * r4(la.g.s.n_feat),
+               ig.dx + (ig.row_off[x.b] + x.r0) * (int64_t)ig.dx_stride, ig.dx_stride);
+}
+
+// ---- integrated gradients on the large path (dr_ginet_large_integrated_grad_pass) ----
+// ginet_integrated_grad_kernel cut at its barriers into launches: group g's
+// step s0_g + j is round j of a (tile, tail) launch pair with grid.y = G, on
+// group g's own Z rows, pooling partials / keys, dz rows and slab / head / out
+// rows (no word is written by two workgroups of a launch, and nothing of the
+// plan's own workspaces is touched); the steps' weighted dZ add up in dz[g]
+// over the rounds, in step order, and one gather launch forms part[g] = A^T
+// dz[g] for ig_finish_kernel.  Stream order is the only ordering between
+// launches.  A workgroup whose group has no step in this round returns before
+// any barrier or store.
+struct IgTileArgs {
+  dr_integrated_grad ig;
+  dr_ig_tiles ws;
+  int round;
+};
+
+// group grp's step of this round, or -1
+__device__ __forceinline__ int ig_tile_step(const IgTileArgs& ia, int grp) {
+  const int s = (int)((int64_t)grp * ia.ig.n_steps / ia.ig.n_groups) + ia.round;
+  return s < (int)((int64_t)(grp + 1) * ia.ig.n_steps / ia.ig.n_groups) ? s : -1;
+}
+
+// la as group grp sees it: the plan's workspaces and the pass's outputs are the group's own
+__device__ __forceinline__ void ig_tile_view(LargeArgs& la, const IgTileArgs& ia, int grp) {
+  const int F = la.g.s.n_feat, OUT = la.g.p.out_dim;
+  const int64_t keys = (int64_t)la.plan.k0_max * 32;
+  la.plan.z = ia.ws.z + (int64_t)grp * ia.ws.rows * r4(F);  // (rows of r4(F) words, as the tile kernel and the tail index plan->z)
+  if (la.plan.part_key) la.plan.part_key = ia.ws.part_key + (int64_t)grp * la.g.B * keys;
+  else {
+    la.plan.part_val = ia.ws.part_val + (int64_t)grp * la.plan.n_tiles * keys;
+    la.plan.part_arg = ia.ws.part_arg + (int64_t)grp * la.plan.n_tiles * keys;
+  }
+  la.g.p.slab = ia.ig.slab + (int64_t)grp * la.g.B * DR_SLAB_STRIDE(F);
+  la.g.p.head = ia.ig.head + (int64_t)grp * la.g.B * DR_HEAD_STRIDE(OUT);
+  la.g.p.out = ia.ig.out + (int64_t)grp * la.g.B * OUT;
+}
+
+__global__ void __launch_bounds__(NTA) ginet_large_ig_conv1_kernel(LargeArgs la, IgTileArgs ia) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int grp = blockIdx.y, s = ig_tile_step(ia, grp);
+  if (s < 0) return;
+  ig_tile_view(la, ia, grp);
+  conv_tile_f32<true>(la, lds, ia.ig.alpha[s], ia.ig.zb, ia.ws.zb_stride);
+}
+
+// Tail: on the group's first step the graph's rows of dz[g] are zeroed; then
+// tail_body as it is, on the group's view; then ginet_integrated_grad_kernel's
+// weighted chain on the global rows (dv = w_s dp1, one fmaf per channel in
+// ascending order), over all K0 F items as ginet_large_input_grad_tail_kernel.
+__global__ void __launch_bounds__(NT) ginet_large_ig_tail_kernel(LargeArgs la, IgTileArgs ia) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int tid = threadIdx.x, b = blockIdx.x, grp = blockIdx.y, s = ig_tile_step(ia, grp);
+  if (s < 0) return;
+  ig_tile_view(la, ia, grp);
+  const int F = la.g.s.n_feat, DS = r4(F);
+  float* dzg = ia.ws.dz + ((int64_t)grp * ia.ws.rows + la.plan.z_row0[b]) * DS;
+  if (ia.round == 0) {  // early: nothing reads dz before the loop below
+    const int n4 = la.g.descs[b].n_nodes * (DS >> 2);
+    float4* z4 = reinterpret_cast<float4*>(dzg);
+    for (int p = tid; p < n4; p += NT) z4[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  tail_body(la, b, lds);
+  __syncthreads();  // the tail's last step (dW1) has read Z; dp1 / a1 are complete, the zeros above are stored
+  const dr_graph_desc d = la.g.descs[b];
+  const int N = d.n_nodes, K0 = d.n_k0;
+  const TailCarve c = tail_carve(K0, d.n_p1, d.n_k1, la.g.s.transpose_aliased, la.g.p.out_dim);
+  const float* dp1 = lds + c.dp1;
+  const int* a1 = reinterpret_cast<const int*>(lds + c.a1);
+  const float ws = ia.ig.weight[s];
+  for (int p = tid; p < K0 * F; p += NT) {
+    const int k = p / F, f = p - k * F;
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const float* wsrc = (hf ? la.g.w.w1e : la.g.w.w1) + f;
+      float w[16], dv[16];
+      int i[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) w[u] = wsrc[u * F];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int4 iv = *reinterpret_cast<const int4*>(a1 + k * 32 + hf * 16 + 4 * q);
+        const float4 vv = *reinterpret_cast<const float4*>(dp1 + k * 32 + hf * 16 + 4 * q);
+        i[4 * q] = iv.x; i[4 * q + 1] = iv.y; i[4 * q + 2] = iv.z; i[4 * q + 3] = iv.w;
+        dv[4 * q] = ws * vv.x; dv[4 * q + 1] = ws * vv.y; dv[4 * q + 2] = ws * vv.z; dv[4 * q + 3] = ws * vv.w;
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (i[u] < N) dzg[i[u] * DS + f] = fmaf(dv[u], w[u], dzg[i[u] * DS + f]);
+    }
+  }
+}
+
+// part[g][part_off[b] + m, :] = ginet_large_dx_kernel's gather of dz[g], grid (n_tiles, G)
+__global__ void __launch_bounds__(NTA) ginet_large_ig_dx_kernel(LargeArgs la, IgTileArgs ia) {
+  const TileCtx x = tile_ctx(la.g.descs, la.plan);
+  const int grp = blockIdx.y, DXS = ia.ig.dx_stride;
+  dx_tile_rows(la.g.s, x, ia.ws.dz + ((int64_t)grp * ia.ws.rows + la.plan.z_row0[x.b]) * r4(la.g.s.n_feat),
+               ia.ig.part + ((int64_t)grp * ia.ig.part_rows + ia.ig.part_off[x.b] + x.r0) * (int64_t)DXS, DXS);
 }
 
 }  // namespace
@@ -2858,6 +2982,62 @@ extern "C" int dr_ginet_large_input_grad_pass(const dr_graph_store* store, const
   hipLaunchKernelGGL(ginet_large_conv1_kernel, dim3(plan->n_tiles), dim3(NTA), conv_lds_bytes, st, la);
   hipLaunchKernelGGL(ginet_large_input_grad_tail_kernel, dim3(n_batch), dim3(NT), tail_lds_bytes, st, la, dz);
   hipLaunchKernelGGL(ginet_large_dx_kernel, dim3(plan->n_tiles), dim3(NTA), 0, st, la, iga, static_cast<const float*>(dz));
+  return (int)hipGetLastError();
+}
+
+extern "C" int dr_ginet_large_integrated_grad_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                                                   const dr_large_plan* plan, const dr_ginet_weights* w, const dr_pass* pass,
+                                                   const dr_integrated_grad* ig, const dr_ig_tiles* ws,
+                                                   int32_t conv_lds_bytes, int32_t tail_lds_bytes, void* stream) {
+  if (!pass || !ig || !ws) return DR_E_ARG;
+  dr_pass gp = *pass;  // the pass as the steps run it: its partials go to the groups' scratch rows
+  gp.slab = ig->slab;
+  gp.head = ig->head;
+  gp.out = ig->out;
+  gp.loss_per_graph = nullptr;  // (one word per graph, which the groups would all write)
+  gp.stamps = nullptr;
+  DR_CHECK(large_pass_check(store, descs, n_batch, plan, w, &gp, conv_lds_bytes, tail_lds_bytes, true));
+  if (!(pass->flags & DR_PASS_BACKWARD)) return DR_E_ARG;
+  if (pass->slot || pass->step_counter) return DR_E_ARG;
+  if (!ig->attr || !ig->row_off || !ig->alpha || !ig->weight || !ig->part || !ig->part_off || !ig->attr_sum ||
+      !ig->slab || !ig->head || !ig->out)
+    return DR_E_ARG;
+  if (ig->n_steps < 1 || ig->n_groups < 1 || ig->n_groups > ig->n_steps) return DR_E_ARG;
+  if (ig->dx_stride < store->n_feat || ig->dx_stride % 4 != 0) return DR_E_ARG;
+  if (reinterpret_cast<uintptr_t>(ig->attr) % 16 != 0 || reinterpret_cast<uintptr_t>(ig->part) % 16 != 0) return DR_E_ARG;
+  if (ig->part_rows < 0) return DR_E_ARG;
+  if ((ig->zb != nullptr) != (ig->xb != nullptr)) return DR_E_ARG;
+  // the tile kernel reads zb rows in 16-byte chunks over r4(F) columns
+  if (ig->zb && (ws->zb_stride < r4(store->n_feat) || ws->zb_stride % 4 != 0 || reinterpret_cast<uintptr_t>(ig->zb) % 16 != 0))
+    return DR_E_ARG;
+  if (!ws->dz || !ws->z || ws->rows < 0) return DR_E_ARG;
+  if (plan->part_key ? !ws->part_key : (!ws->part_val || !ws->part_arg)) return DR_E_ARG;
+  if (reinterpret_cast<uintptr_t>(ws->dz) % 16 != 0 || reinterpret_cast<uintptr_t>(ws->z) % 16 != 0) return DR_E_ARG;
+  if (!store->cl0 || !store->t_rowptr || !store->t_col) return DR_E_ARG;
+  if (n_batch == 0) return DR_OK;
+  if (!store->x) return DR_E_ARG;
+  DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_large_ig_conv1_kernel)));
+  DR_CHECK(dr_allow_big_lds(reinterpret_cast<const void*>(&ginet_large_ig_tail_kernel)));
+  LargeArgs la;
+  la.g.s = *store;
+  la.g.w = *w;
+  la.g.p = gp;
+  la.g.descs = descs;
+  la.g.B = n_batch;
+  la.plan = *plan;
+  IgTileArgs ia;
+  ia.ig = *ig;
+  ia.ws = *ws;
+  hipStream_t st = (hipStream_t)stream;
+  const int G = ig->n_groups, R = (ig->n_steps + G - 1) / G;  // the longest range of steps
+  for (ia.round = 0; ia.round < R; ++ia.round) {
+    hipLaunchKernelGGL(ginet_large_ig_conv1_kernel, dim3(plan->n_tiles, G), dim3(NTA), conv_lds_bytes, st, la, ia);
+    hipLaunchKernelGGL(ginet_large_ig_tail_kernel, dim3(n_batch, G), dim3(NT), tail_lds_bytes, st, la, ia);
+  }
+  ia.round = 0;
+  hipLaunchKernelGGL(ginet_large_ig_dx_kernel, dim3(plan->n_tiles, G), dim3(NTA), 0, st, la, ia);
+  DR_CHECK((int)hipGetLastError());
+  hipLaunchKernelGGL(ig_finish_kernel, dim3(n_batch), dim3(NTF), 0, st, la.g.s, descs, ia.ig);
   return (int)hipGetLastError();
 }
 

@@ -254,6 +254,12 @@ class IntegratedGradC(ctypes.Structure):
                 ("attr_sum", VP), ("slab", VP), ("head", VP), ("out", VP)]  # fmt: skip
 
 
+class IgTilesC(ctypes.Structure):
+    """dr_ig_tiles: the per-group workspaces of dr_ginet_large_integrated_grad_pass."""
+
+    _fields_ = [("dz", VP), ("z", VP), ("part_key", VP), ("part_val", VP), ("part_arg", VP), ("rows", ctypes.c_int64), ("zb_stride", ctypes.c_int32), ("pad0", ctypes.c_int32)]
+
+
 class ReduceMemberC(ctypes.Structure):
     """dr_reduce_member: what dr_reduce_update_opt takes, for one model of dr_reduce_multi_build."""
 
@@ -289,6 +295,7 @@ SIGNATURES = [
     ("dr_ensemble_score", ctypes.c_int, [VP, ctypes.c_int64, VP, ctypes.c_int64, VP, ctypes.c_int64, _c_i32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, VP, ctypes.c_int32, VP, VP, VP]),
     ("dr_ginet_large_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(LargePlanC), ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.c_int32, ctypes.c_int32, VP]),
     ("dr_ginet_large_input_grad_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(LargePlanC), ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.POINTER(InputGradC), VP, ctypes.c_int32, ctypes.c_int32, VP]),
+    ("dr_ginet_large_integrated_grad_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(LargePlanC), ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), ctypes.POINTER(IntegratedGradC), ctypes.POINTER(IgTilesC), ctypes.c_int32, ctypes.c_int32, VP]),
     ("dr_ginet_large_conv_lds_bytes", ctypes.c_int64, [ctypes.c_int32] * 5),
     ("dr_ginet_nocluster_large_pass", ctypes.c_int, [ctypes.POINTER(GraphStoreC), VP, ctypes.c_int32, ctypes.POINTER(NcPlanC), ctypes.POINTER(GinetWeightsC), ctypes.POINTER(PassC), VP]),
     ("dr_nc_large_scratch_floats", ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),

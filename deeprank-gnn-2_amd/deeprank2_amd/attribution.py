@@ -33,7 +33,13 @@ a baseline to ``x`` (Sundararajan et al. 2017): on the reference model, one
 aggregates first and ``Z = A x`` is linear in ``x``, so every node of the path
 is the Z-input pass on a rescaled Z block, and one
 ``dr_ginet_integrated_grad_pass`` runs all of them for a batch; the layer route
-runs the steps one by one for the batches that pass does not take.
+runs the steps one by one for the batches that pass does not take.  Graphs
+beyond one workgroup's LDS have the tile route here too
+(``integrated_gradients(..., tiles=True)``,
+``dr_ginet_large_integrated_grad_pass``): every step is the large-graph path's
+tile kernel on the rescaled Z and its tail, the steps' ``dZ`` are summed in a
+global workspace per group of steps and gathered once; the same bits as the
+single-workgroup pass on graphs both take.
 """
 
 from __future__ import annotations
@@ -272,6 +278,18 @@ def _tile_plan(rq: _Request, h: BatchHandle):
         return None
 
 
+def _route(tiles, plan, fits):
+    """The route of one batch, ``"tiles"``, ``"fused"`` or ``"layers"``, from
+    ``tiles`` (checked), the batch's tile plan (None: it fails the tile checks,
+    or ``tiles`` is off) and whether its largest graph fits the
+    single-workgroup pass.  Pure host function."""
+    if plan is not None and (tiles == "force" or not fits):
+        return "tiles"
+    if fits and (plan is not None or not tiles):
+        return "fused"
+    return "layers"
+
+
 def _input_grad_tiles(rq: _Request, c, h: BatchHandle, plan, s, e):
     """One ``dr_ginet_large_input_grad_pass`` (three launches): the batch's rows of ``dx`` in place."""
     if c.dz is None:  # dZ of the largest batch, rows of r4(F) words
@@ -333,15 +351,14 @@ def input_gradients(model, dataset, indices=None, batch_size=64, target=None, se
         zs = rq.store.agg_x_stride if z is not None else 0
         plan = _tile_plan(rq, h) if tiles else None
         fits = rq.kernel_ok and not h.nonfinite and _lds("dr_ginet_input_grad_lds_bytes", h, rq.out_dim, zs) <= LDS_MAX
-        if plan is not None and (tiles == "force" or not fits):
+        route = _route(tiles, plan, fits)
+        if route == "tiles":
             _input_grad_tiles(rq, c, h, plan, s, e)
-            rq.taken.add("tiles")
-        elif fits and (plan is not None or not tiles):
+        elif route == "fused":
             _input_grad_fused(rq, c, h, s, e, z, zs)
-            rq.taken.add("fused")
         else:
             _input_grad_layers(rq, h, s, e)
-            rq.taken.add("layers")
+        rq.taken.add(route)
     return InputGradients(rq.view, rq.out, rq.seed_t, rq.node_off, rq.idx, rq.path())
 
 
@@ -354,6 +371,14 @@ def input_gradients(model, dataset, indices=None, batch_size=64, target=None, se
 # profiles/integrated_gradients/bench_ig.txt); capped by the step count, never
 # by the batch, so a graph gets the same bits alone and inside a batch.
 IG_GROUPS_DEFAULT = 4
+
+# The same for dr_ginet_large_integrated_grad_pass (the tile route), where a
+# group is a row of the grid of every launch: the fastest of {1, 2, 4, 8, 32} at
+# 32 steps on a batch of 8 atom-level graphs (DESIGN §5 "Integrated gradients
+# on tiles", profiles/integrated_gradients_large/bench_ig_large.txt: more
+# groups shorten the rounds but ig_finish_kernel, one workgroup per graph,
+# reads every group's rows); capped by the step count, never by the batch.
+IG_TILE_GROUPS_DEFAULT = 2
 
 QUADRATURES = ("gausslegendre", "midpoint")
 
@@ -392,7 +417,7 @@ class IntegratedGradients(_NodeRows):
     delta: torch.Tensor  # [n] fp64: attr_sum - (out - out_baseline) . seed, the completeness gap (quadrature error)
     node_off: np.ndarray  # host int64 [n + 1]: graph i's rows are node_off[i] .. node_off[i + 1] - 1
     indices: np.ndarray  # host int64 [n]: the graphs' positions in the store
-    path: str  # "fused", "layers" or "mixed"
+    path: str  # "fused", "tiles", "layers" or "mixed" (more than one route)
     alpha: np.ndarray  # host fp32 [steps]: the quadrature nodes the device used
     weight: np.ndarray  # host fp32 [steps]: the quadrature weights the device used
 
@@ -438,36 +463,89 @@ def _check_ig_args(model, steps, method, groups, baseline, quad):
     return alpha.astype(np.float32), weight.astype(np.float32), int(groups)
 
 
-def _integrated_fused(rq: _Request, c, h: BatchHandle, s, e):
-    """The Z-input forward at ``x``, the same at the baseline, and one
-    ``dr_ginet_integrated_grad_pass``: the batch's rows of ``attr`` in place."""
-    f, out_dim, dev, n_groups, zs = rq.f, rq.out_dim, rq.dev, c.n_groups, c.zs
-    if c.slab is None:  # per-group slab / head / out of the training pass and the partial rows: scratch, made on the first fused batch
-        c.slab = torch.empty(n_groups * rq.bmax * ginet.slab_stride(f), dtype=torch.float32, device=dev)
-        c.head = torch.zeros(n_groups * rq.bmax * ginet.head_stride(out_dim), dtype=torch.float32, device=dev)
-        c.outs = torch.empty(n_groups * rq.bmax * out_dim, dtype=torch.float32, device=dev)
-        c.part = torch.empty((n_groups, max(c.rmax, 1), rq.xs), dtype=torch.float32, device=dev)
-    _forward_z(h, rq.w, out_dim, c.z_all, zs, rq.out[s:e])
-    if c.zb is not None:
-        _forward_z(h, rq.w, out_dim, c.zb, zs, c.out_b[s:e])
-    else:
+def _group_scratch(rq: _Request, c, n_groups):
+    """Per-group slab / head / out of the training pass and the partial rows of a fused route: scratch, made on the route's first batch."""
+    f, out_dim, dev = rq.f, rq.out_dim, rq.dev
+    return SimpleNamespace(
+        n_groups=n_groups,
+        slab=torch.empty(n_groups * rq.bmax * ginet.slab_stride(f), dtype=torch.float32, device=dev),
+        head=torch.zeros(n_groups * rq.bmax * ginet.head_stride(out_dim), dtype=torch.float32, device=dev),
+        outs=torch.empty(n_groups * rq.bmax * out_dim, dtype=torch.float32, device=dev),
+        part=torch.empty((n_groups, max(c.rmax, 1), rq.xs), dtype=torch.float32, device=dev),
+    )
+
+
+def _baseline_out_and_seed(rq: _Request, c, s, e):
+    """After the forward at ``x`` (and at a given baseline): a zero baseline's outputs in closed form, and the ``"pred"`` seed."""
+    if c.xb is None:
         if c.out_b0 is None:  # a zero baseline's outputs: Z = 0 pools to zero features, so the head on a zero vector
             c.out_b0 = torch.relu(rq.params[13]) @ rq.params[14].t() + rq.params[15]
         c.out_b[s:e] = c.out_b0
     if rq.target == "pred":
         rq.seed_t[s:e] = _one_hot_pred(rq.out[s:e])
-    p = make_pass(out_dim, _lib.DR_PASS_FORWARD | _lib.DR_PASS_BACKWARD, dout=rq.seed_t[s:e])
+
+
+def _integrated_args(rq: _Request, c, g, s, e):
+    """What the two fused routes hand their entry alike: the seeded pass and the ``dr_integrated_grad`` of the batch's rows, on the group scratch ``g``."""
+    p = make_pass(rq.out_dim, _lib.DR_PASS_FORWARD | _lib.DR_PASS_BACKWARD, dout=rq.seed_t[s:e])
     ig = _lib.IntegratedGradC()
     ig.attr, ig.row_off, ig.dx_stride = rq.buf.data_ptr(), c.offs.data_ptr() + 8 * s, rq.xs
-    ig.n_steps, ig.n_groups = c.n_steps, n_groups
+    ig.n_steps, ig.n_groups = c.n_steps, g.n_groups
     ig.alpha, ig.weight = c.quad_t.data_ptr(), c.quad_t.data_ptr() + 4 * c.n_steps
     ig.zb, ig.xb = _lib.ptr(c.zb), _lib.ptr(c.xb) if c.zb is not None else None
-    ig.part, ig.part_off, ig.part_rows = c.part.data_ptr(), c.offs.data_ptr() + 8 * (rq.n + s), c.part.shape[1]
+    ig.part, ig.part_off, ig.part_rows = g.part.data_ptr(), c.offs.data_ptr() + 8 * (rq.n + s), g.part.shape[1]
     ig.attr_sum = c.attr_sum.data_ptr() + 8 * s
-    ig.slab, ig.head, ig.out = c.slab.data_ptr(), c.head.data_ptr(), c.outs.data_ptr()
+    ig.slab, ig.head, ig.out = g.slab.data_ptr(), g.head.data_ptr(), g.outs.data_ptr()
+    return p, ig
+
+
+def _integrated_fused(rq: _Request, c, h: BatchHandle, s, e):
+    """The Z-input forward at ``x``, the same at the baseline, and one
+    ``dr_ginet_integrated_grad_pass``: the batch's rows of ``attr`` in place."""
+    out_dim, dev, zs = rq.out_dim, rq.dev, c.zs
+    if c.fused is None:
+        c.fused = _group_scratch(rq, c, c.n_groups)
+    _forward_z(h, rq.w, out_dim, c.z_all, zs, rq.out[s:e])
+    if c.zb is not None:
+        _forward_z(h, rq.w, out_dim, c.zb, zs, c.out_b[s:e])
+    _baseline_out_and_seed(rq, c, s, e)
+    p, ig = _integrated_args(rq, c, c.fused, s, e)
     lds = _lds("dr_ginet_integrated_grad_lds_bytes", h, out_dim, zs)
     rc = _lib.load().dr_ginet_integrated_grad_pass(rq.store.cstruct(), h.descs.data_ptr(), h.B, rq.w, p, ig, c.z_all.data_ptr(), zs, lds, _lib.stream_ptr(dev))
     _lib.check(rc, "dr_ginet_integrated_grad_pass")
+
+
+def _integrated_tiles(rq: _Request, c, h: BatchHandle, plan, s, e):
+    """The large-graph forward at ``x``, the same at the baseline (the store
+    struct with ``x`` pointing at it), and one
+    ``dr_ginet_large_integrated_grad_pass``: the batch's rows of ``attr`` in place."""
+    out_dim, dev, lib = rq.out_dim, rq.dev, _lib.load()
+    t = c.tiles
+    if t is None:  # the groups' scratch and workspaces for the largest batch, made on the first tile batch
+        c.tiles = t = _group_scratch(rq, c, c.n_groups_tiles)
+        rows, g = max(c.rmax, 1), t.n_groups
+        t.dz = torch.empty(g * rows * (-(-rq.f // 4) * 4), dtype=torch.float32, device=dev)
+        t.z = torch.empty(g * rows * rq.xs, dtype=torch.float32, device=dev)
+        t.keys = torch.zeros(g * rq.bmax * K0_TILES_MAX * 32, dtype=torch.int64, device=dev)  # zero between passes, as LargePlan's
+        t.part_val = t.part_arg = None
+    if not plan.c.part_key and (t.part_val is None or t.part_val.numel() < t.n_groups * plan.n_tiles * plan.k0_max * 32):
+        t.part_val = torch.empty(t.n_groups * plan.n_tiles * plan.k0_max * 32, dtype=torch.float32, device=dev)
+        t.part_arg = torch.empty(t.n_groups * plan.n_tiles * plan.k0_max * 32, dtype=torch.int32, device=dev)
+
+    def forward(store_c, out):
+        p = make_pass(out_dim, _lib.DR_PASS_FORWARD, out=out)
+        _lib.check(lib.dr_ginet_large_pass(store_c, h.descs.data_ptr(), h.B, plan.c, rq.w, p, plan.conv_lds, plan.tail_lds, _lib.stream_ptr(dev)), "dr_ginet_large_pass")
+
+    forward(rq.store.cstruct(), rq.out[s:e])
+    if c.xb is not None:
+        forward(c.store_b, c.out_b[s:e])
+    _baseline_out_and_seed(rq, c, s, e)
+    p, ig = _integrated_args(rq, c, t, s, e)
+    ws = _lib.IgTilesC()
+    ws.dz, ws.z, ws.rows, ws.zb_stride = t.dz.data_ptr(), t.z.data_ptr(), max(c.rmax, 1), c.zs
+    ws.part_key, ws.part_val, ws.part_arg = t.keys.data_ptr(), _lib.ptr(t.part_val), _lib.ptr(t.part_arg)
+    rc = lib.dr_ginet_large_integrated_grad_pass(rq.store.cstruct(), h.descs.data_ptr(), h.B, plan.c, rq.w, p, ig, ws, plan.conv_lds, plan.tail_lds, _lib.stream_ptr(dev))
+    _lib.check(rc, "dr_ginet_large_integrated_grad_pass")
 
 
 def _integrated_layers(rq: _Request, c, h: BatchHandle, s, e):
@@ -491,7 +569,7 @@ def _integrated_layers(rq: _Request, c, h: BatchHandle, s, e):
     c.attr_sum[s:e] = torch.zeros(e - s, dtype=torch.float64, device=rq.dev).index_add_(0, t.batch.long(), a.double().sum(dim=1))
 
 
-def integrated_gradients(model, dataset, indices=None, batch_size=64, target=None, seed=None, baseline=None, steps=32, method="gausslegendre", groups=None, fused=None, *, attr_out=None, _quadrature=None) -> IntegratedGradients:
+def integrated_gradients(model, dataset, indices=None, batch_size=64, target=None, seed=None, baseline=None, steps=32, method="gausslegendre", groups=None, fused=None, *, tiles=None, attr_out=None, _quadrature=None, _large=None) -> IntegratedGradients:
     """Integrated gradients (Sundararajan et al. 2017) of ``out . seed`` with
     respect to the node features, for the graphs ``indices`` of ``dataset``:
 
@@ -503,9 +581,8 @@ def integrated_gradients(model, dataset, indices=None, batch_size=64, target=Non
     quadrature's error, which ``delta`` reports per graph.
 
     ``model``, ``dataset``, ``indices``, ``batch_size``, ``target``, ``seed``,
-    ``fused``: as :func:`input_gradients` (``"pred"`` is decided once, from the
-    forward at ``x``; there is no ``tiles`` here: graphs beyond one workgroup's
-    LDS stay on the layer route).  ``baseline``: ``None`` (zeros: the dataset mean of
+    ``fused``, ``tiles``: as :func:`input_gradients` (``"pred"`` is decided
+    once, from the forward at ``x``).  ``baseline``: ``None`` (zeros: the dataset mean of
     standardised features), an ``[F]`` vector given to every node, or a
     ``[rows, F]`` tensor in the request's node order (no graph may then be
     requested twice).  ``groups``: workgroups per graph of the fused pass, each
@@ -519,13 +596,33 @@ def integrated_gradients(model, dataset, indices=None, batch_size=64, target=Non
     ``dr_ginet_integrated_grad_pass``.  The others run ``steps`` times
     ``layered.ginet_forward`` + ``torch.autograd.grad`` with the same nodes and
     weights.  The ``edge_attr`` attribution is exactly zero (module docstring)
-    and is not returned."""
+    and is not returned.
+
+    ``tiles`` (default ``TILES_DEFAULT``, off): with ``True``, a batch that
+    passes :func:`input_gradients`' tile checks runs
+    ``dr_ginet_large_integrated_grad_pass`` (``path`` ``"tiles"``) when
+    ``dr_ginet_integrated_grad_lds_bytes`` of its largest graph exceeds one
+    workgroup's LDS, and the single-workgroup pass when it does not; a batch
+    that fails the checks takes the layer route.  ``"force"``: every batch
+    that passes the checks takes the tile route (the two fused routes write
+    equal bits at equal ``groups``).  There ``out`` and ``out_baseline`` come
+    from forward ``dr_ginet_large_pass`` launches (a zero baseline: the closed
+    form), and ``groups`` defaults to ``IG_TILE_GROUPS_DEFAULT`` (at most
+    ``steps``): a group is a row of the grid of each of the ``2 R + 2`` launches,
+    ``R = ceil(steps / groups)``.  The tile plan is built once per batch; the
+    groups' workspaces are allocated once per call for the largest batch, per
+    group about ``rows * (x_stride + r4(F) + x_stride) * 4`` bytes (its Z rows,
+    its running ``dZ`` and its partial ``attr`` rows; ``rows``: the batch's
+    nodes) plus 16 KiB of pooling keys per graph, beside the slab / head
+    scratch every fused route has."""
     _check_target("integrated_gradients", model, target, seed)
+    tiles = _check_tiles(tiles)
     alpha, weight, n_groups = _check_ig_args(model, steps, method, groups, baseline, _quadrature)
     rq = _Request("integrated_gradients", model, dataset, indices, batch_size, target, seed, fused, attr_out, "attr_out")
     # once per call: the baseline in x's layout (xb) and its neighbour sums in Z's (zb), the buffers beside the request's, the offsets and the quadrature on the device
     store, dev, f, n, node_off, batches = rq.store, rq.dev, rq.f, rq.n, rq.node_off, rq.batches
-    c = SimpleNamespace(alpha=alpha, weight=weight, n_steps=int(alpha.size), n_groups=n_groups, xb=None, zb=None, out_b0=None, slab=None)
+    c = SimpleNamespace(alpha=alpha, weight=weight, n_steps=int(alpha.size), n_groups=n_groups, xb=None, zb=None, out_b0=None, fused=None, tiles=None, store_b=None)
+    c.n_groups_tiles = n_groups if groups is not None else min(IG_TILE_GROUPS_DEFAULT, c.n_steps)
     c.z_all = store.agg_x() if rq.kernel_ok else None  # None: there is no gather form, every batch takes the layer route
     c.zs = store.agg_x_stride
     if baseline is not None:
@@ -541,9 +638,9 @@ def integrated_gradients(model, dataset, indices=None, batch_size=64, target=Non
                 msg = "a per-node baseline needs every requested graph named once"
                 raise ValueError(msg)
             xb[_store_rows(store, rq.idx, dev), :f] = b_t
-        if c.z_all is not None:
-            c.zb = torch.empty_like(c.z_all)
-            st = _lib.GraphStoreC.from_buffer_copy(store.cstruct())
+        if c.z_all is not None or (tiles and rq.kernel_ok):  # (the tile route gathers Z itself and reads only zb)
+            c.zb = torch.empty((xb.shape[0], c.zs), dtype=torch.float32, device=dev)  # Z's layout
+            c.store_b = st = _lib.GraphStoreC.from_buffer_copy(store.cstruct())  # the store at the baseline
             st.x = xb.data_ptr()
             _lib.check(_lib.load().dr_aggregate_x(st, c.zb.data_ptr(), c.zs, 0, store.n_graphs, _lib.stream_ptr(dev)), "dr_aggregate_x")
     c.out_b = torch.empty(n, rq.out_dim, dtype=torch.float32, device=dev)
@@ -556,13 +653,19 @@ def integrated_gradients(model, dataset, indices=None, batch_size=64, target=Non
     c.quad_t = torch.from_numpy(np.stack([alpha, weight])).to(dev)  # [2, S]
     for s, e in batches:
         h = rq.handle(s, e)
+        if _large is not None:  # (the tests' knob: the plan's tile size and forms)
+            h.large_tile, h.large_halos, h.large_atomic_max = _large["tile"], _large["halos"], _large["atomic_max"]
         lds = _lds("dr_ginet_integrated_grad_lds_bytes", h, rq.out_dim, c.zs) if c.z_all is not None else -1
-        if c.z_all is not None and not h.nonfinite and 0 <= lds <= LDS_MAX:
+        fits = c.z_all is not None and not h.nonfinite and 0 <= lds <= LDS_MAX
+        plan = _tile_plan(rq, h) if tiles else None
+        route = _route(tiles, plan, fits)
+        if route == "tiles":
+            _integrated_tiles(rq, c, h, plan, s, e)
+        elif route == "fused":
             _integrated_fused(rq, c, h, s, e)
-            rq.taken.add("fused")
         else:
             _integrated_layers(rq, c, h, s, e)
-            rq.taken.add("layers")
+        rq.taken.add(route)
     delta = c.attr_sum - ((rq.out.double() - c.out_b.double()) * rq.seed_t.double()).sum(dim=1)
     return IntegratedGradients(rq.view, rq.out, c.out_b, rq.seed_t, c.attr_sum, delta, rq.node_off, rq.idx, rq.path(), alpha, weight)
 

@@ -582,6 +582,67 @@ int dr_ginet_large_input_grad_pass(const dr_graph_store* store, const dr_graph_d
                                    const dr_input_grad* ig, float* dz,
                                    int32_t conv_lds_bytes, int32_t tail_lds_bytes, void* stream);
 
+/* GINet integrated gradients (dr_ginet_integrated_grad_pass above) for graphs
+ * larger than one workgroup's LDS: the same attr and attr_sum, from the same
+ * operations in the same order, with that entry's loop over the steps cut into
+ * launches.  Group g owns the steps [g S / G, (g + 1) S / G) (integer floors),
+ * ascending; R = ceil(S / G) is the longest range.  2 R + 2 launches on the
+ * caller's stream, ordered by the stream alone (no arrival counters, no
+ * polling, no wait between workgroups):
+ *   round j = 0 .. R - 1, group g at step s = g S / G + j (a workgroup whose
+ *   group has no such step returns before any barrier or store):
+ *     1. grid (plan->n_tiles, G): dr_ginet_large_pass's tile kernel, each
+ *        gathered 16-byte chunk of Z rescaled before the MFMA and the Z store
+ *        read it: alpha_s Z for a zero baseline, else fmaf(alpha_s, Z - Zb, Zb)
+ *        with Zb from ig->zb (the single-workgroup entry's expressions); the
+ *        partial maxima (or keys) and the flagged Z rows go to group g's
+ *        workspaces;
+ *     2. grid (n_batch, G): on j = 0 the graph's rows of dz[g] are zeroed; then
+ *        dr_ginet_large_pass's tail on group g's workspaces and scratch rows;
+ *        then dv = w_s dp1 and dz[g][a1[k, ch], f] = fmaf(dv[k, ch],
+ *        [W1; W1e][ch, f], dz[g][a1[k, ch], f]), ch ascending, a1 >= N skipped;
+ *   2 R + 1. grid (plan->n_tiles, G): dr_ginet_large_input_grad_pass's gather
+ *        of dz[g] into rows part_off[b] .. of part[g];
+ *   2 R + 2. dr_ginet_integrated_grad_pass's second launch, unchanged.
+ * On graphs dr_ginet_integrated_grad_pass takes as well, attr and attr_sum hold
+ * that entry's bits at the same n_groups, for every tile size and either form
+ * of the plan (halos, part_key).  No atomics beyond the tile kernel's order-free
+ * max keys, no word written by two workgroups of a launch: repeated calls give
+ * equal bits.  The plan's own z, part_val, part_arg and part_key are neither
+ * read nor written: a training pass and this pass may share one plan.
+ * ig: as dr_ginet_integrated_grad_pass (slab, head and out hold group g's rows
+ * of the tail's partials); ig->zb has rows of ws->zb_stride words (the
+ * store-wide A xb, dr_aggregate_x on a store whose x is xb).  There is no z
+ * argument: the tile kernel gathers Z = A x itself.
+ * ws: the groups' workspaces, contents undefined on entry and on exit but for
+ * part_key.  Per group about rows (x_stride + r4(F)) 4 bytes plus the keys
+ * (B k0_max 256 bytes) or the partials (n_tiles k0_max 256 bytes).
+ * plan, conv_lds_bytes, tail_lds_bytes: as dr_ginet_large_pass; neither kernel
+ * takes more LDS than that entry's.
+ * Refused before any launch: everything dr_ginet_large_input_grad_pass and
+ * dr_ginet_integrated_grad_pass refuse (but for the latter's z); DR_E_ARG for
+ * a NULL ws, dz or z, a NULL part_key with a plan that has keys, a NULL
+ * part_val or part_arg with one that has none, a dz or z that is not 16-byte
+ * aligned, rows < 0, zb without xb or xb without zb, a zb that is not 16-byte
+ * aligned or whose zb_stride is below r4(F) or not a multiple of 4, n_groups
+ * outside 1 .. n_steps; DR_E_UNSUPPORTED for compute_dtype != DR_DTYPE_F32.
+ * n_batch == 0: DR_OK once the arguments pass, nothing launched.  No
+ * allocation, no host synchronisation: capturable.                           */
+typedef struct dr_ig_tiles {
+  float* dz;          /* [G, rows, r4(F)] fp32, 16-byte aligned: each group's running dZ sum     */
+  float* z;           /* [G, rows, x_stride] fp32, 16-byte aligned: each group's plan->z          */
+  uint64_t* part_key; /* [G, B, k0_max, 32], zero on entry and left zero: with plan->part_key    */
+  float* part_val;    /* [G, n_tiles, k0_max, 32]: without plan->part_key                        */
+  int32_t* part_arg;  /* [G, n_tiles, k0_max, 32]: without plan->part_key                        */
+  int64_t rows;       /* rows per group of dz and z: at least plan->z_row0[B]                    */
+  int32_t zb_stride;  /* row stride of ig->zb (a multiple of 4, >= r4(F)); unused without zb      */
+  int32_t pad0;
+} dr_ig_tiles;
+int dr_ginet_large_integrated_grad_pass(const dr_graph_store* store, const dr_graph_desc* descs, int32_t n_batch,
+                                        const dr_large_plan* plan, const dr_ginet_weights* w, const dr_pass* pass,
+                                        const dr_integrated_grad* ig, const dr_ig_tiles* ws,
+                                        int32_t conv_lds_bytes, int32_t tail_lds_bytes, void* stream);
+
 /* ---- FoutNet (deeprank2/neuralnets/gnn/foutnet.py:72-118) ---------------- */
 
 /* FoutNet weights, all row-major as the torch parameters are stored.       */

@@ -33,6 +33,11 @@ rules.
 ``--ig`` measures integrated gradients instead (``main_ig``: the bare
 ``dr_ginet_integrated_grad_pass`` for each group count, the public call, and
 the layer route as the baseline), by the same rules.
+
+``--ig --large`` measures integrated gradients on the tile route
+(``main_ig_large``: the bare ``dr_ginet_large_integrated_grad_pass`` for each
+group count, the public call with ``tiles=True``, and the layer route as the
+baseline) on the ``--large`` batch.
 """
 
 from __future__ import annotations
@@ -280,14 +285,147 @@ def main_large(args):
     print(json.dumps({"bench": "attribution_large", "B": nb, "reps": args.reps, "runs": args.runs, "rows": rows_j, "tiles_win": wins, "five_spreads_us": round(margin, 2), "epilogue_us": round(epi, 2)}))
 
 
+IG_LARGE_REPS = 3  # calls per timing of --ig --large: the layer route takes about half a second per call
+IG_LARGE_BARE = 5  # launches of a bare pass per call
+
+
+def main_ig_large(args):
+    """``--ig --large``: integrated gradients of graphs beyond one workgroup's
+    LDS, the ``--large`` batch, 32 Gauss-Legendre nodes, zero baseline.
+
+    * ``pass_gG``        the bare ``dr_ginet_large_integrated_grad_pass`` (all
+                         ``2 ceil(32 / G) + 2`` launches) with G groups, G in 1, 2,
+                         4, 8, 32, the handle, the plan and the workspaces kept
+                         (``IG_LARGE_BARE`` passes per call, us per pass);
+    * ``pass_forward``   the bare forward ``dr_ginet_large_pass`` on the same plan
+                         (what the public call adds for ``out``);
+    * ``api_tiles``      ``integrated_gradients(model, store, batch, tiles=True)``;
+    * ``api_layers``     the default call: 32 times ``layered.ginet_forward`` +
+                         ``torch.autograd.grad``, the only route the parent offers
+                         these graphs: the baseline."""
+    dev = torch.device("cuda:0")
+    nb = LARGE_B
+    store = GraphStore(pack_graphs(records(make_graphs("atom", nb, 1000))), dev)
+    torch.manual_seed(0)
+    model = ginet.GINet(30, 1, 3).to(dev).eval()
+    idx = np.arange(nb)
+    f, xs, out_dim = store.n_feat, store.x_stride, 1
+
+    def api_tiles():
+        return attribution.integrated_gradients(model, store, indices=idx, batch_size=nb, steps=IG_STEPS, tiles=True)
+
+    def api_layers():
+        return attribution.integrated_gradients(model, store, indices=idx, batch_size=nb, steps=IG_STEPS)
+
+    a = api_tiles()
+    assert a.path == "tiles"
+    if not args.pass_only:  # (a trace holds the tile route's kernels only)
+        b = api_layers()
+        assert b.path == "layers"
+        scale = float(b.attr.abs().max())
+        assert torch.allclose(a.attr, b.attr, rtol=1e-4, atol=max(1e-6, 1e-6 * scale)) and torch.allclose(a.out, b.out, rtol=1e-4, atol=1e-4), "the two routes agree"
+    print(f"completeness: max |delta| {float(a.delta.abs().max()):.3e} against a mean sum|attr| of {float(a.attr.abs().sum()) / nb:.3e} per graph")
+
+    h = BatchHandle(store, idx.astype(np.int32))
+    plan = h.large_plan(out_dim)
+    params = [p.detach().contiguous() for p in model.ordered_params()]
+    w = ginet.weights_c(params)
+    lib = _lib.load()
+    stream = _lib.stream_ptr(dev)
+    seed = torch.ones(nb, out_dim, device=dev)
+    p = make_pass(out_dim, _lib.DR_PASS_FORWARD | _lib.DR_PASS_BACKWARD, dout=seed)
+    out = torch.empty(nb, out_dim, device=dev)
+    pf = make_pass(out_dim, _lib.DR_PASS_FORWARD, out=out)
+    rows = int(a.node_off[-1])
+    attr = torch.empty(rows, xs, device=dev)
+    off = torch.from_numpy(a.node_off[:-1].copy()).to(dev)
+    alpha, weight = torch.from_numpy(a.alpha).to(dev), torch.from_numpy(a.weight).to(dev)
+    attr_sum = torch.empty(nb, dtype=torch.float64, device=dev)
+    gmax = max(IG_GROUPS)
+    slab = torch.empty(gmax * nb * ginet.slab_stride(f), device=dev)
+    head = torch.zeros(gmax * nb * ginet.head_stride(out_dim), device=dev)
+    outs = torch.empty(gmax * nb * out_dim, device=dev)
+    part = torch.empty(gmax, rows, xs, device=dev)
+    dz = torch.empty(gmax * rows * (-(-f // 4) * 4), device=dev)
+    zg = torch.empty(gmax * rows * xs, device=dev)
+    keys = torch.zeros(gmax * nb * plan.k0_max * 32, dtype=torch.int64, device=dev)
+    assert plan.c.part_key, "the default plan has keys"
+
+    def bare(groups):
+        ig, ws = _lib.IntegratedGradC(), _lib.IgTilesC()
+        ig.attr, ig.row_off, ig.dx_stride = attr.data_ptr(), off.data_ptr(), xs
+        ig.n_steps, ig.n_groups = IG_STEPS, groups
+        ig.alpha, ig.weight = alpha.data_ptr(), weight.data_ptr()
+        ig.part, ig.part_off, ig.part_rows = part.data_ptr(), off.data_ptr(), rows
+        ig.attr_sum = attr_sum.data_ptr()
+        ig.slab, ig.head, ig.out = slab.data_ptr(), head.data_ptr(), outs.data_ptr()
+        ws.dz, ws.z, ws.part_key, ws.rows = dz.data_ptr(), zg.data_ptr(), keys.data_ptr(), rows
+
+        def body():
+            for _ in range(IG_LARGE_BARE):
+                _lib.check(lib.dr_ginet_large_integrated_grad_pass(store.cstruct(), h.descs.data_ptr(), nb, plan.c, w, p, ig, ws, plan.conv_lds, plan.tail_lds, stream), "dr_ginet_large_integrated_grad_pass")
+
+        return body
+
+    def pass_forward():
+        for _ in range(IG_LARGE_BARE):
+            _lib.check(lib.dr_ginet_large_pass(store.cstruct(), h.descs.data_ptr(), nb, plan.c, w, pf, plan.conv_lds, plan.tail_lds, stream), "dr_ginet_large_pass")
+
+    gdef = min(attribution.IG_TILE_GROUPS_DEFAULT, IG_STEPS)
+    bare(gdef)()
+    torch.cuda.synchronize()
+    assert torch.equal(attr[:, :f], a.attr), "the bare pass writes the public call's bits"
+
+    if args.pass_only:  # for a kernel trace: nothing but bare passes from here on
+        body = bare(args.pass_only)
+        for _ in range(args.reps):
+            body()
+        torch.cuda.synchronize()
+        print(f"{args.reps * IG_LARGE_BARE} bare passes with {args.pass_only} groups")
+        return
+
+    n, e, k0 = (v[idx] for v in store._sizes[:3])  # noqa: SLF001
+    print(f"B = {nb} atom-level graphs: N {int(n.min())}-{int(n.max())}, E {int(e.min())}-{int(e.max())}, K0 {int(k0.min())}-{int(k0.max())}; tiles of {plan.TILE} rows, {plan.n_tiles} tiles; S = {IG_STEPS}; reps {args.reps} ({args.reps * IG_LARGE_BARE} bare passes), runs {args.runs}")
+    variants = {f"pass_g{g}": bare(g) for g in IG_GROUPS}
+    variants["pass_forward"] = pass_forward
+    variants["api_tiles"] = api_tiles
+    variants["api_layers"] = api_layers
+    times = interleaved(variants, args.runs, args.reps)
+    for name in times:
+        if name.startswith("pass_"):
+            times[name] = [t / IG_LARGE_BARE for t in times[name]]
+    rows_j = []
+    print(f"{'variant':>12} {'us/batch':>12} {'spread us':>10}  runs")
+    for name, ts in times.items():
+        mean, spread = float(np.mean(ts)), float(max(ts) - min(ts))
+        rows_j.append({"variant": name, "us": round(mean, 2), "spread_us": round(spread, 2), "runs_us": [round(x, 2) for x in ts]})
+        print(f"{name:>12} {mean:12.1f} {spread:10.1f}  {' '.join(f'{x:.1f}' for x in ts)}")
+    best = min(IG_GROUPS, key=lambda g: np.mean(times[f"pass_g{g}"]))
+    print(f"fastest groups: {best} (the default is {attribution.IG_TILE_GROUPS_DEFAULT})")
+    print(f"per step, one group (pass_g1 / {IG_STEPS}): {float(np.mean(times['pass_g1'])) / IG_STEPS:.2f} us")
+    n_, o_ = times["api_tiles"], times["api_layers"]
+    margin = 5 * (max(o_) - min(o_))
+    wins = bool(np.mean(o_) - np.mean(n_) > margin)
+    print(f"api_tiles {np.mean(n_):.1f} us against api_layers {np.mean(o_):.1f} us, 5 x the baseline's spread {margin:.1f} us -> {'tiles win' if wins else 'no win'}")
+    print(f"the baseline's spread is {100 * (max(o_) - min(o_)) / np.mean(o_):.1f} % of its mean (wanted: under 10 %)")
+    device_us = float(np.mean(times[f"pass_g{gdef}"]) + np.mean(times["pass_forward"]))
+    print(f"api_tiles split: device {device_us:.1f} us (pass_g{gdef} + pass_forward), host {float(np.mean(n_)) - device_us:.1f} us (the plan, the workspaces, the launches' enqueue)")
+    print(json.dumps({"bench": "integrated_gradients_large", "B": nb, "steps": IG_STEPS, "reps": args.reps, "runs": args.runs, "rows": rows_j, "fastest_groups": best,
+                      "default_groups": attribution.IG_TILE_GROUPS_DEFAULT, "tiles_win": wins, "five_spreads_us": round(margin, 2), "device_us": round(device_us, 2)}))  # fmt: skip
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--reps", type=int, default=None, help="calls per timing (default 200: the layer route's timing window is over a second; --large: 10, the layer route is slow on atom-level graphs)")
+    ap.add_argument("--reps", type=int, default=None, help="calls per timing (default 200: the layer route's timing window is over a second; --large: 10, the layer route is slow on atom-level graphs; --ig --large: 3)")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--ig", action="store_true", help="measure integrated gradients (main_ig) instead of the input gradients")
     ap.add_argument("--large", action="store_true", help="measure the tile route on atom-level graphs (main_large)")
+    ap.add_argument("--pass-only", type=int, default=0, metavar="G", help="with --ig --large: after the checks, only --reps x 5 bare passes with G groups (for a kernel trace)")
     args = ap.parse_args()
-    args.reps = args.reps or (LARGE_REPS if args.large else 200)
+    args.reps = args.reps or ((IG_LARGE_REPS if args.ig else LARGE_REPS) if args.large else 200)
+    if args.ig and args.large:
+        main_ig_large(args)
+        return
     if args.large:
         main_large(args)
         return
